@@ -2,12 +2,19 @@
 """Headline benchmark: Mpaths/s of the HIP path tracer on N MI355X GPUs.
 
     python bench.py                      # 1 GPU: BASELINE configs[1], 5 steps, 1 warmup
+    python bench.py --full               # the same, then everything else the benchmark measures and checks (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one full pass of the hot path over the workload with the scene already resident in HBM: zero the film,
 trace every camera path of the sample window, splat, and -- for N > 1 -- sum the film over the ranks with one RCCL
 all-reduce.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, W warmup steps, K timed steps, --dump-outputs DIR if given (the
+film accumulators of the last step, see dump_outputs), the line.  Everything else -- the roofline and the instrumented
+launch its counters come from, the exact-ties and stream-sampler rates, the other BASELINE configurations, the feature
+scenes, the CPU baselines and the L2 checks, the one-GPU baseline of an N-GPU line -- runs only under --full, after
+(or, for the counters, before) the timed region.
 
 Workloads (--workload):
   bunny  BASELINE configs[1]: bunny.json, 512x512 film (516x516 sampled px), 256 spp, max_ray_depth 8 = 68,161,536
@@ -16,10 +23,10 @@ Workloads (--workload):
          film, 256 spp, max_ray_depth 8 = 270,536,704 paths per step.  The default for N > 1, as north_star words it:
          "image tiles shard across the 8 GPUs of one node with a final RCCL reduce of Film tiles".
   cornell / ao  BASELINE configs[2] / configs[4].
-At N = 1 the default run also renders ONE full-size step of each of the other three configurations after the headline's
+At N = 1 a --full run also renders full-size steps of each of the other three configurations after the headline's
 timed region (`other_configs` in the line), so that every BASELINE configuration has a number the driver saw.
 
-Roofline (`roofline` in the line): SURVEY.md 8(d)'s figure -- algorithmic bytes of the dominant kernel over its measured
+Roofline (`roofline` in a --full line): SURVEY.md 8(d)'s figure -- algorithmic bytes of the dominant kernel over its measured
 launch time against the 8 TB/s HBM peak -- with the HBM bytes that really moved (`traffic`, PMC) beside it.  The scenes are
 cache resident, so the kernel is not HBM bound; what the counters say does bound it is under `roofline.issue`: VALU
 wave-instructions per second against the MEASURED issue peak of this chip (profiles/valu_issue_peak.json, tools/valu_peak.py)
@@ -583,6 +590,31 @@ def feature_scenes(device_index, seed, torch):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20261003
+
+
+def dump_outputs(out_dir, accum):
+    """--dump-outputs: what a caller of the timed path receives after the last step -- the film accumulators {sum w*rgb, sum w}
+    per pixel, (yres, xres, 4) float32, summed over the ranks for N > 1 -- as <out_dir>/film.npy.  A film larger than
+    DUMP_LIMIT_BYTES (configs[4]'s 2048x2048) is written as a fixed, seeded sample of its pixels instead: film_sample.npy
+    (n, 4) float32 and the flat pixel index of each row, film_sample_index.npy (n,) float64.  Returns the files written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    if accum.nbytes <= DUMP_LIMIT_BYTES:
+        path = os.path.join(out_dir, "film.npy")
+        np.save(path, accum)
+        return [path]
+    flat = accum.reshape(-1, accum.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 4096) // (flat.shape[1] * 4 + 8)   # (room for the two .npy headers)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[0], size=n, replace=False))
+    paths = [os.path.join(out_dir, "film_sample.npy"), os.path.join(out_dir, "film_sample_index.npy")]
+    np.save(paths[0], flat[idx])
+    np.save(paths[1], idx.astype(np.float64))
+    return paths
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -593,11 +625,18 @@ def main():
     ap.add_argument("--resolution", type=int, nargs=2, default=None)
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / l2 legs")
-    ap.add_argument("--no-others", action="store_true", help="skip the full-size steps of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: roofline and counters, exact-ties and stream-sampler rates, other "
+                         "BASELINE configurations, feature scenes, CPU baselines, L2 checks, the one-GPU baseline of N > 1")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline / l2 legs")
+    ap.add_argument("--no-others", action="store_true", help="with --full: skip the full-size steps of the other BASELINE configurations")
     ap.add_argument("--schedule", choices=["auto", "wavefront", "megakernel"], default="auto")
     ap.add_argument("--dump-film", default=None, help="rank 0 saves the film accumulators of the last step (reduced, N > 1) as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path computed in its last step to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -622,15 +661,16 @@ def main():
     base_seed = 20261003
     part = gd.shard_for(rank, world, "samples" if scaling == "weak" else "tiles", base_seed)
 
-    # counters for the roofline (one instrumented launch, outside the timed region;
-    # the sampler is counter-based so every timed launch does exactly this work)
-    counted = counters_of(wl, part["seed"], part["shard"], args.schedule,
-                          scale_from_spp=64 if (scene.spp() > 256 and wl.standard) else None)
-    counted_note = counted.pop("_scaled_from_spp", None)
-    my_paths = counted["paths"]
+    counted, counted_note = None, None
+    if args.full:
+        # counters for the roofline (one instrumented launch, outside the timed region;
+        # the sampler is counter-based so every timed launch does exactly this work)
+        counted = counters_of(wl, part["seed"], part["shard"], args.schedule,
+                              scale_from_spp=64 if (scene.spp() > 256 and wl.standard) else None)
+        counted_note = counted.pop("_scaled_from_spp", None)
 
     one_gpu_ms = None
-    if world > 1 and rank == 0 and scaling == "strong":
+    if args.full and world > 1 and rank == 0 and scaling == "strong":
         # the WHOLE frame on one GPU, outside the timed region: the N-GPU line then carries its own strong-scaling baseline
         whole = tracer.new_film()
         wl.render_frame(whole, seed=base_seed, schedule=args.schedule)
@@ -645,14 +685,26 @@ def main():
     if world > 1:   # set the communicator up outside the timed region even when --warmup is 0
         gd.allreduce_film(torch.zeros(16, device=tracer.device))
         gd.barrier()
+    # the last step is also asked what it did: paths traced (this rank's share) and the schedule AUTO resolved to.  That reads
+    # the library's own event time after the call's kernels, where the step ends in a device synchronise anyway.
+    calls, last = [0], {}
+
+    def render():
+        calls[0] += 1
+        r = wl.render_frame(seed=part["seed"], shard=part["shard"], schedule=args.schedule, timed=calls[0] == args.warmup + args.steps)
+        if r["stats"]:
+            last.update(r["stats"])
+
     elapsed, per_step = run_steps(
-        render=lambda: wl.render_frame(seed=part["seed"], shard=part["shard"], schedule=args.schedule),
-        zero_film=film.zero_, allreduce=lambda: gd.allreduce_film(film.accum), barrier=gd.barrier, sync=torch.cuda.synchronize,
+        render=render, zero_film=film.zero_, allreduce=lambda: gd.allreduce_film(film.accum), barrier=gd.barrier, sync=torch.cuda.synchronize,
         steps=args.steps, warmup=args.warmup, world=world, make_event=lambda: torch.cuda.Event(enable_timing=True))
     my_elapsed = elapsed
+    my_paths, my_schedule = int(last["paths"]), int(last["schedule"])
     if args.dump_film and rank == 0:
         import numpy as np
         np.save(args.dump_film, film.accum.detach().cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, film.accum.detach().cpu().numpy())
     call_ms = [a for a, _ in per_step]          # device events around gbl_render (the launch stream)
     reduce_ms = [b for _, b in per_step]
     my_trace_ms = sum(call_ms) / len(call_ms)
@@ -665,7 +717,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(paths, op=dist.ReduceOp.SUM)
         # per rank: device time of the trace, of the reduce, paths traced and the schedule the library resolved AUTO to
-        mine = torch.tensor([my_trace_ms, sum(reduce_ms) / len(reduce_ms), float(my_paths), float(counted.get("schedule", 0)), my_elapsed * 1e3 / args.steps],
+        mine = torch.tensor([my_trace_ms, sum(reduce_ms) / len(reduce_ms), float(my_paths), float(my_schedule), my_elapsed * 1e3 / args.steps],
                             dtype=torch.float64, device=red_dev)
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
@@ -684,18 +736,9 @@ def main():
             sys.exit(3)
 
     # what AUTO resolved to: the library reports the schedule a call ran under (gbl_stats.schedule)
-    resolved = args.schedule if args.schedule != "auto" else {1: "megakernel", 2: "wavefront"}.get(counted.get("schedule"), "megakernel")
+    resolved = args.schedule if args.schedule != "auto" else {1: "megakernel", 2: "wavefront"}.get(my_schedule, "megakernel")
     if rank == 0:
-        timings = tracer.timings(args.steps * len(wl.bands))                      # HIP events inside the library, per kernel class and call
-        main_ms = [x[0] for x in timings] or call_ms
-        avg_kernel_ms = sum(main_ms) / args.steps if timings else sum(main_ms) / len(main_ms)   # per step (a step is len(bands) calls)
-        pmc, pmc_note = (pmc_for(wl_name, resolved, wl.integrator, scene.spp()) if (wl.standard and world == 1) else (None, "non-standard run: no counters quoted"))
-        rays = counted["extension_rays"] + counted["shadow_rays"]
         value = job_paths * args.steps / elapsed * 1e-6
-        roofline = roofline_object(counted, avg_kernel_ms, pmc, pmc_note, wl.kernel_label(resolved), waves_per_simd=5 if resolved == "wavefront" else 3)
-        roofline["call_ms_avg"] = round(sum(call_ms) / len(call_ms), 3)
-        if counted_note:
-            roofline["counters_note"] = "counted by an instrumented launch at %d spp and scaled to the frame's %d" % (counted_note, scene.spp())
         line = {
             "metric": "Mpaths/sec at 512x512x256spp (GoblinPathtracer hot path, bunny.json, max_ray_depth 8)" if wl_name == "bunny" and wl.standard
                       else "Mpaths/sec at %dx%dx%dspp (GoblinPathtracer hot path, %s.json, max_ray_depth %d)" % (wl.res[0], wl.res[1], scene.spp(), wl.scene_name, wl.depth),
@@ -714,15 +757,25 @@ def main():
                 "workload": wl.describe(),
                 "schedule": resolved,
                 "paths_per_step": int(job_paths),
-                "rays_per_path": round(rays / max(1, my_paths), 3),
-                "mrays_per_s": round(value * rays / max(1, my_paths), 2),
                 "sampler": "native counter-based, reference stratification law",
                 "sharding": ({"weak": "whole window per rank, seed+rank, one film all-reduce",
                               "strong": "8x8 tiles interleaved over ranks (rank r owns tiles t = r mod N), one film all-reduce"}[scaling]
                              if world > 1 else "single GPU"),
             },
-            "roofline": roofline,
         }
+        if args.full:
+            timings = tracer.timings(args.steps * len(wl.bands))                      # HIP events inside the library, per kernel class and call
+            main_ms = [x[0] for x in timings] or call_ms
+            avg_kernel_ms = sum(main_ms) / args.steps if timings else sum(main_ms) / len(main_ms)   # per step (a step is len(bands) calls)
+            pmc, pmc_note = (pmc_for(wl_name, resolved, wl.integrator, scene.spp()) if (wl.standard and world == 1) else (None, "non-standard run: no counters quoted"))
+            rays = counted["extension_rays"] + counted["shadow_rays"]
+            roofline = roofline_object(counted, avg_kernel_ms, pmc, pmc_note, wl.kernel_label(resolved), waves_per_simd=5 if resolved == "wavefront" else 3)
+            roofline["call_ms_avg"] = round(sum(call_ms) / len(call_ms), 3)
+            if counted_note:
+                roofline["counters_note"] = "counted by an instrumented launch at %d spp and scaled to the frame's %d" % (counted_note, scene.spp())
+            line["config"]["rays_per_path"] = round(rays / max(1, my_paths), 3)
+            line["config"]["mrays_per_s"] = round(value * rays / max(1, my_paths), 2)
+            line["roofline"] = roofline
         if world > 1:
             try:
                 import torch.cuda.nccl as tnccl
@@ -746,7 +799,7 @@ def main():
                 line["config"]["one_gpu_same_workload"] = {"ms_per_step": round(one_gpu_ms, 3), "mpaths_per_s": round(job_paths / one_gpu_ms * 1e-3, 2),
                                                            "speedup": round(one_gpu_ms / (elapsed / args.steps * 1e3), 3),
                                                            "note": "rank 0 alone, whole frame, outside the timed region"}
-        if world == 1 and wl.standard and resolved == "megakernel":
+        if args.full and world == 1 and wl.standard and resolved == "megakernel":
             # the same steps with the reference's exact-t tie rule kept in the lean kernel (gbl_render_params.exact_ties): what the
             # headline would post if it resolved the ~5 ties per 10^7 paths as the replay / stream kernels do
             try:
@@ -764,7 +817,7 @@ def main():
                                            "note": "gbl_render_params.exact_ties = 1: the lean quad kernel following the reference's exact-t tie rule and reachability test (trace.h GBL_TIE_DETECT: a flag in the loops, one check per query, an exact retrace of the rare ray)"}
             except Exception as e:
                 print("value_tie_exact leg failed: %s" % e, file=sys.stderr)
-        if world == 1 and wl_name == "bunny":
+        if args.full and world == 1 and wl_name == "bunny":
             # the same frame with the reference's own mt19937 sample stream generated on the device (GBL_SAMPLES_STREAM):
             # its Film is the reference binary's; reported beside the headline, never as `value`
             try:
@@ -782,7 +835,7 @@ def main():
                 del sfilm
             except Exception as e:
                 print("reference_stream_sampler leg failed: %s" % e, file=sys.stderr)
-        if world == 1 and wl_name == "bunny" and wl.standard and not args.no_others:
+        if args.full and world == 1 and wl_name == "bunny" and wl.standard and not args.no_others:
             # every other BASELINE configuration, one full-size step each, outside the headline's timed region
             line["other_configs"] = {}
             host_cores = max(1, len(os.sched_getaffinity(0)))
@@ -793,9 +846,9 @@ def main():
                 except Exception as e:
                     line["other_configs"][other] = {"error": str(e)}
                     print("other_configs[%s] failed: %s" % (other, e), file=sys.stderr)
-        if world == 1 and wl_name == "bunny" and wl.standard and not args.no_others:
+        if args.full and world == 1 and wl_name == "bunny" and wl.standard and not args.no_others:
             line["feature_scenes"] = feature_scenes(device_index, base_seed, torch)
-        if world == 1 and wl_name == "bunny" and not args.no_cpu:
+        if args.full and world == 1 and wl_name == "bunny" and not args.no_cpu:
             # every host core this process may run on (the reference defaults to hardware_concurrency, GoblinThreadPool.cpp:5-10)
             cores = max(1, len(os.sched_getaffinity(0)))
             # the CPU leg renders the FULL workload when the box has the cores to do it in ~15-30 s (68 M paths at
