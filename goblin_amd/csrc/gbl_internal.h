@@ -14,6 +14,12 @@
 #include "device_scene.h"
 #include "kernels/wf_args.h"
 
+// A device buffer of the context, grown on demand (gbl_api.hip grow()) and freed by gbl_destroy
+struct gbl_buf {
+    void* p = nullptr;
+    uint64_t bytes = 0;
+};
+
 struct gbl_ctx {
     int device = 0;
     std::string error;
@@ -21,10 +27,6 @@ struct gbl_ctx {
     DevScene scene;
     gbl_info info;
     uint32_t* work_counter = nullptr;
-    void* prim_buf = nullptr;         // the primary pass's hits: entries x (float4 + int32)
-    uint64_t prim_entries = 0;
-    uint32_t* prim_items = nullptr;   // ... and its word per work item of the path kernel (RenderArgs::prim_items)
-    uint64_t prim_items_cap = 0;
     unsigned long long* stats = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int num_cus = 256;
@@ -32,23 +34,21 @@ struct gbl_ctx {
     void* rccl_allreduce = nullptr;
     // wavefront pool (allocated on first use)
     uint32_t wf_pool = 0;
-    uint32_t* wf_spill = nullptr;   // wf_ensure_spill()
     hipStream_t wf_aux = nullptr;   // shadow rays of iteration k trace here while the main stream traces extension rays k+1
     hipEvent_t wf_ev_shade = nullptr, wf_ev_shadow = nullptr;
-    int wf_spill_levels = 0;
     WfArgs wf;
-    float4* wf_li = nullptr;
-    size_t wf_li_entries = 0;
     uint64_t li_budget = 0;   // li_budget_bytes()
-    uint32_t* stream_seeds = nullptr;     // GBL_SAMPLES_STREAM: per-tile mt19937 seeds of the full sample window
-    uint32_t* stream_scratch = nullptr;   // ... and the workgroups' sample-generation scratch
-    uint64_t stream_scratch_bytes = 0;
-    float* stream_xy = nullptr;           // ... and the image position of every camera sample of the call (for the splat)
-    uint64_t stream_xy_bytes = 0;
-    float* vol_buf = nullptr;    // per-sample {transmittance, Lv} of the render in flight (scenes with a participating medium)
-    uint64_t vol_entries = 0;
-    float4* sss_buf = nullptr;   // per-sample Lsubsurface of the render in flight (scenes with subsurface materials)
-    uint64_t sss_entries = 0;
+    uint32_t* stream_seeds = nullptr;   // GBL_SAMPLES_STREAM: per-tile mt19937 seeds of the full sample window
+    // buffers of the render in flight
+    gbl_buf li;               // per-sample radiance (float4) when the caller passes no li_out
+    gbl_buf prim_hits;        // the primary pass's hits: entries x (float4 + int32)
+    gbl_buf prim_items;       // ... and its word per work item of the path kernel (RenderArgs::prim_items)
+    gbl_buf vol;              // per-sample {transmittance, Lv} (scenes with a participating medium)
+    gbl_buf sss;              // per-sample Lsubsurface (scenes with subsurface materials)
+    gbl_buf stream_scratch;   // GBL_SAMPLES_STREAM: the workgroups' sample-generation scratch ...
+    gbl_buf stream_xy;        // ... and the image position of every camera sample of the call (for the splat)
+    gbl_buf wf_spill;         // the wavefront trace stacks' levels beyond LDS (wf_ensure_spill) ...
+    int wf_spill_levels = 0;  // ... how many it holds
     std::map<int, float> auto_rays_per_path;   // GBL_SCHEDULE_AUTO's pilot: rays per camera path by 2 * max_ray_depth + russian_roulette (gbl_render)
     double build_ms = 0.0;    // pack_scene + BVH construction + node / triangle upload
     // what gbl_update_instances needs to rebuild the TLAS
