@@ -123,6 +123,101 @@ __device__ __forceinline__ void camera_differentials(const DevCamera& c, float i
     *dyd = quat_rotate(c.q, normalize(dy_view));
 }
 
+// ---------------------------------------------------------------------------
+// The camera sample of (pixel, k), for every kernel that starts or retraces a camera ray, or splats where one landed: the copies
+// must agree bit for bit.
+// ---------------------------------------------------------------------------
+// Pixel `pix` (row-major in the 8x8 tile) of the launch's owned tile `lt` (tiles t with t % shard_count == shard_index).
+__device__ __forceinline__ void tile_pixel(const RenderArgs& ra, uint32_t lt, uint32_t pix, int* px, int* py) {
+    const uint32_t tile = ra.shard_index + lt * ra.shard_count;
+    const int tx = tile % ra.tiles_x, ty = tile / ra.tiles_x;
+    *px = ra.window[0] + GBL_TILE * tx + static_cast<int>(pix % 8u);
+    *py = ra.window[2] + GBL_TILE * ty + static_cast<int>(pix / 8u);
+}
+
+// Index of pixel (px, py) in the render window, row-major: li_out, li_defer and the replay records are pixel-major
+// (index * spp + k).
+__device__ __forceinline__ uint32_t window_pixel(const RenderArgs& ra, int px, int py) {
+    return static_cast<uint32_t>((py - ra.window[2]) * (ra.window[1] - ra.window[0]) + (px - ra.window[0]));
+}
+
+// The native law's key of pixel (px, py): its index in the FULL sample window, so a sub-window or a shard draws what the whole
+// frame would.
+__device__ __forceinline__ uint32_t native_pixel_key(const DevScene& sc, const RenderArgs& ra, int px, int py) {
+    const int full_w = sc.film.window[1] - sc.film.window[0];
+    return nat_mix(ra.seed_key, static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0])));
+}
+
+// Where the draws of camera sample k of pixel (px, py) come from.  REPLAY: `rec` is the sample's record (replay and stream
+// samplers); otherwise the native law, keyed by the pixel.
+template <bool REPLAY>
+__device__ __forceinline__ SampleSource camera_source(const DevScene& sc, const RenderArgs& ra, int px, int py, uint32_t k, const float* rec) {
+    SampleSource src;
+    src.spp = ra.spp;
+    src.root = ra.root;
+    src.rec = REPLAY ? rec : nullptr;
+    src.pixel_key = REPLAY ? 0u : native_pixel_key(sc, ra, px, py);
+    src.k = k;
+    return src;
+}
+
+// The image position of the camera sample `src` of pixel (px, py): the record's first two floats, or the native law's pattern 0,
+// which is not permuted (sample k sits in sub-cell k).
+template <bool REPLAY>
+__device__ __forceinline__ void image_position(const SampleSource& src, int px, int py, float* image_x, float* image_y) {
+    if (REPLAY) {
+        *image_x = src.rec[0];
+        *image_y = src.rec[1];
+    } else {
+        float u, v;
+        src.native_2d(0u, 1u, 0u, false, &u, &v);
+        *image_x = px + u;
+        *image_y = py + v;
+    }
+}
+
+// The position part of camera sample k of pixel (px, py): the source of its draws and its image position.
+template <bool REPLAY>
+__device__ __forceinline__ SampleSource camera_position(const DevScene& sc, const RenderArgs& ra, int px, int py, uint32_t k, const float* rec,
+                                                        float* image_x, float* image_y) {
+    const SampleSource src = camera_source<REPLAY>(sc, ra, px, py, k, rec);
+    image_position<REPLAY>(src, px, py, image_x, image_y);
+    return src;
+}
+
+// Sample::lensU1/2: drawn by the EXT builds (and the Whitted, medium and subsurface kernels) where the camera has a lens -- the
+// record's or the native law's pattern 1; the lean builds pass 0.
+template <bool EXT, bool REPLAY>
+__device__ __forceinline__ void camera_lens(const DevCamera& c, const SampleSource& src, float* lens_u1, float* lens_u2) {
+    *lens_u1 = 0.0f;
+    *lens_u2 = 0.0f;
+    if (EXT && c.lens_radius != 0.0f) {
+        if (REPLAY) {
+            *lens_u1 = src.rec[2];
+            *lens_u2 = src.rec[3];
+        } else {
+            src.native_2d(1u, 1u, 0u, true, lens_u1, lens_u2);
+        }
+    }
+}
+
+// The ray part: the lens draw and Camera::generateRay.
+template <bool EXT, bool REPLAY>
+__device__ __forceinline__ void camera_sample_ray(const DevCamera& c, const SampleSource& src, float image_x, float image_y, F3* o, F3* d, float* mint) {
+    float lens_u1, lens_u2;
+    camera_lens<EXT, REPLAY>(c, src, &lens_u1, &lens_u2);
+    camera_ray<EXT>(c, image_x, image_y, lens_u1, lens_u2, o, d, mint);
+}
+
+// Both parts: camera sample k of pixel (px, py) with its camera ray.
+template <bool EXT, bool REPLAY>
+__device__ __forceinline__ SampleSource camera_sample(const DevScene& sc, const RenderArgs& ra, int px, int py, uint32_t k, const float* rec,
+                                                      float* image_x, float* image_y, F3* o, F3* d, float* mint) {
+    const SampleSource src = camera_position<REPLAY>(sc, ra, px, py, k, rec, image_x, image_y);
+    camera_sample_ray<EXT, REPLAY>(sc.camera, src, *image_x, *image_y, o, d, mint);
+    return src;
+}
+
 // TexFrag differentials of a hit: the camera ray's for the primary hit, none afterwards (RayDifferential(p, wi, eps)
 // carries no auxiliary rays, GoblinRay.h:48-51).
 template <bool REPLAY>
@@ -130,15 +225,8 @@ __device__ __forceinline__ void hit_differentials(const DevScene& sc, const Samp
                                                   const Frag& fr, TexFrag& tf) {
     F3 dxo = f3(0, 0, 0), dxd = dxo, dyo = dxo, dyd = dxo;
     if (primary) {
-        float lens_u1 = 0.0f, lens_u2 = 0.0f;
-        if (sc.camera.lens_radius != 0.0f) {
-            if (REPLAY) {
-                lens_u1 = src.rec[2];
-                lens_u2 = src.rec[3];
-            } else {
-                src.native_2d(1u, 1u, 0u, true, &lens_u1, &lens_u2);
-            }
-        }
+        float lens_u1, lens_u2;
+        camera_lens<true, REPLAY>(sc.camera, src, &lens_u1, &lens_u2);
         camera_differentials(sc.camera, image_x, image_y, lens_u1, lens_u2, &dxo, &dxd, &dyo, &dyd);
     }
     uv_differential(fr, tf, primary, dxo, dxd, dyo, dyd);

@@ -11,41 +11,18 @@ __global__ __launch_bounds__(GBL_BLOCK) void vol_kernel(DevScene sc, RenderArgs 
     LaneCounters cnt = {};
     const uint64_t per_tile = 64ull * static_cast<uint64_t>(ra.spp);
     const uint64_t total = static_cast<uint64_t>(ra.local_tiles) * per_tile;
-    const int sub_w = ra.window[1] - ra.window[0];
-    const int full_w = sc.film.window[1] - sc.film.window[0];
     for (uint64_t id = static_cast<uint64_t>(blockIdx.x) * GBL_BLOCK + threadIdx.x; id < total; id += static_cast<uint64_t>(gridDim.x) * GBL_BLOCK) {
         const uint32_t lt = static_cast<uint32_t>(id / per_tile), r = static_cast<uint32_t>(id % per_tile);
         const uint32_t pix = r / static_cast<uint32_t>(ra.spp), k = r % static_cast<uint32_t>(ra.spp);
-        const uint32_t tile = ra.shard_index + lt * ra.shard_count;
-        const int tx = tile % ra.tiles_x, ty = tile / ra.tiles_x;
-        const int px = ra.window[0] + GBL_TILE * tx + static_cast<int>(pix % 8u), py = ra.window[2] + GBL_TILE * ty + static_cast<int>(pix / 8u);
+        int px, py;
+        tile_pixel(ra, lt, pix, &px, &py);
         if (px >= ra.window[1] || py >= ra.window[3]) continue;
-        const uint32_t out_index = static_cast<uint32_t>((py - ra.window[2]) * sub_w + (px - ra.window[0])) * ra.spp + k;
-        SampleSource src;
-        src.spp = ra.spp;
-        src.root = ra.root;
-        src.rec = nullptr;
-        src.pixel_key = 0;
-        src.k = k;
-        float image_x, image_y, lens_u1 = 0.0f, lens_u2 = 0.0f;
-        if (REPLAY) {
-            src.rec = ra.replay + static_cast<size_t>(out_index) * ra.dims;
-            image_x = src.rec[0];
-            image_y = src.rec[1];
-            lens_u1 = src.rec[2];
-            lens_u2 = src.rec[3];
-        } else {
-            const uint32_t pixel = static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0]));
-            src.pixel_key = nat_mix(ra.seed_key, pixel);
-            float u, v;
-            src.native_2d(0u, 1u, 0u, false, &u, &v);
-            image_x = px + u;
-            image_y = py + v;
-            if (sc.camera.lens_radius != 0.0f) src.native_2d(1u, 1u, 0u, true, &lens_u1, &lens_u2);
-        }
+        const uint32_t out_index = window_pixel(ra, px, py) * ra.spp + k;
+        float image_x, image_y;
         F3 o, d;
         float mint;
-        camera_ray<true>(sc.camera, image_x, image_y, lens_u1, lens_u2, &o, &d, &mint);
+        camera_sample<true, REPLAY>(sc, ra, px, py, k, REPLAY ? ra.replay + static_cast<size_t>(out_index) * ra.dims : nullptr, &image_x, &image_y, &o, &d,
+                                    &mint);
         // the camera ray as Li leaves it: clipped at the first surface -- unless Li returned before its first query
         // (PathTracer::Li without lights, GoblinPathtracer.cpp:53-56)
         float maxt = INFINITY;

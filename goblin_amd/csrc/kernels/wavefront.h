@@ -11,8 +11,8 @@
 //
 // and a final wf_splat per pass that filters the per-sample radiance into the film
 // through the LDS tile.  The arithmetic is the megakernel's (same shade.h / trace.h
-// device functions, same operation order): both schedules give the same per-sample
-// radiance bit for bit, and tests run both.
+// device functions, same operation order, the camera sample of render_kernels.h): both
+// schedules give the same per-sample radiance bit for bit, and tests run both.
 //
 // There is NOT ONE same-address global atomic on the timed path (a returning atomic on
 // a single word saturates near 88 per microsecond on this chip, which throttled the
@@ -75,14 +75,10 @@ __device__ __forceinline__ PathId decode_path(const RenderArgs& ra, const WfArgs
     uint32_t per_tile = 64u * static_cast<uint32_t>(wa.pass_spp);
     uint32_t lt = id / per_tile, r = id % per_tile;
     uint32_t pix = r / wa.pass_spp, kk = r % wa.pass_spp;
-    uint32_t tile = ra.shard_index + lt * ra.shard_count;
-    int tx = tile % ra.tiles_x, ty = tile / ra.tiles_x;
-    p.px = ra.window[0] + GBL_TILE * tx + static_cast<int>(pix % 8u);
-    p.py = ra.window[2] + GBL_TILE * ty + static_cast<int>(pix / 8u);
+    tile_pixel(ra, lt, pix, &p.px, &p.py);
     p.k = static_cast<uint32_t>(wa.pass_k0) + kk;
     // pixel-major over the render window (the C ABI's li_out order when the pass is the whole render)
-    const int sub_w = ra.window[1] - ra.window[0];
-    p.li_index = static_cast<uint32_t>((p.py - ra.window[2]) * sub_w + (p.px - ra.window[0])) * wa.pass_spp + kk;
+    p.li_index = window_pixel(ra, p.px, p.py) * wa.pass_spp + kk;
     p.valid = p.px < ra.window[1] && p.py < ra.window[3];
     return p;
 }
@@ -274,8 +270,7 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_shade(DevScene sc, RenderArgs ra
     auto pixel_key_of = [&](uint32_t index) {
         const uint32_t pix = index / static_cast<uint32_t>(wa.pass_spp);
         const int px = ra.window[0] + static_cast<int>(pix % static_cast<uint32_t>(sub_w_id)), py = ra.window[2] + static_cast<int>(pix / static_cast<uint32_t>(sub_w_id));
-        const int full_w = sc.film.window[1] - sc.film.window[0];
-        return nat_mix(ra.seed_key, static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0])));
+        return native_pixel_key(sc, ra, px, py);
     };
     if (!wa.init) {
         const uint2 id = wa.s_id[slot];
@@ -335,17 +330,10 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_shade(DevScene sc, RenderArgs ra
                 if (EXT && sc.materials[sc.instances[hit.inst].material].has_tex != 0u) {
                     float image_x = 0.0f, image_y = 0.0f;
                     if (ps.bounce < 0) {   // the camera sample this path started from (wf regeneration below)
-                        if (REPLAY) {
-                            image_x = src.rec[0];
-                            image_y = src.rec[1];
-                        } else {
-                            const int sub_w = ra.window[1] - ra.window[0];
-                            const uint32_t pix = out_index / static_cast<uint32_t>(wa.pass_spp);
-                            float u, v;
-                            src.native_2d(0u, 1u, 0u, false, &u, &v);
-                            image_x = (ra.window[0] + static_cast<int>(pix % sub_w)) + u;
-                            image_y = (ra.window[2] + static_cast<int>(pix / sub_w)) + v;
-                        }
+                        const int sub_w = ra.window[1] - ra.window[0];
+                        const uint32_t pix = out_index / static_cast<uint32_t>(wa.pass_spp);
+                        image_position<REPLAY>(src, ra.window[0] + static_cast<int>(pix % sub_w), ra.window[2] + static_cast<int>(pix / sub_w), &image_x,
+                                               &image_y);
                     }
                     hit_differentials<REPLAY>(sc, src, ps.bounce < 0, image_x, image_y, fr, tf);
                 }
@@ -603,34 +591,11 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_shade(DevScene sc, RenderArgs ra
                 if (block != WF_BLOCK_NONE && id < wa.total_paths) {
                     PathId pid = decode_path(ra, wa, static_cast<uint32_t>(id));
                     if (pid.valid) {   // (a pixel clipped off an edge tile leaves the slot EMPTY: it asks again next iteration)
-                        const int full_w = sc.film.window[1] - sc.film.window[0];
                         float image_x, image_y;
                         out_index = pid.li_index;
                         k = pid.k;
-                        src.k = k;
-                        if (REPLAY) {
-                            src.rec = ra.replay + (static_cast<size_t>(out_index / wa.pass_spp) * ra.spp + k) * ra.dims;
-                            image_x = src.rec[0];
-                            image_y = src.rec[1];
-                        } else {
-                            uint32_t pixel = static_cast<uint32_t>((pid.py - sc.film.window[2]) * full_w + (pid.px - sc.film.window[0]));
-                            pixel_key = nat_mix(ra.seed_key, pixel);
-                            src.pixel_key = pixel_key;
-                            float u, v;
-                            src.native_2d(0u, 1u, 0u, false, &u, &v);
-                            image_x = pid.px + u;
-                            image_y = pid.py + v;
-                        }
-                        float lens_u1 = 0.0f, lens_u2 = 0.0f;
-                        if (EXT && sc.camera.lens_radius != 0.0f) {
-                            if (REPLAY) {
-                                lens_u1 = src.rec[2];
-                                lens_u2 = src.rec[3];
-                            } else {
-                                src.native_2d(1u, 1u, 0u, true, &lens_u1, &lens_u2);
-                            }
-                        }
-                        camera_ray<EXT>(sc.camera, image_x, image_y, lens_u1, lens_u2, &ps.o, &ps.d, &ps.mint);
+                        const float* rec = REPLAY ? ra.replay + (static_cast<size_t>(out_index / wa.pass_spp) * ra.spp + k) * ra.dims : nullptr;
+                        src = camera_sample<EXT, REPLAY>(sc, ra, pid.px, pid.py, k, rec, &image_x, &image_y, &ps.o, &ps.d, &ps.mint);
                         ps.throughput = f3(1.0f, 1.0f, 1.0f);
                         ps.Li = f3(0.0f, 0.0f, 0.0f);
                         ps.Ld = f3(0.0f, 0.0f, 0.0f);
@@ -714,8 +679,6 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra
     const int tx = tile_id % ra.tiles_x, ty = tile_id / ra.tiles_x;
     const int px0 = ra.window[0] + GBL_TILE * tx, py0 = ra.window[2] + GBL_TILE * ty;
     const int tx0 = px0 - sc.film.halo, ty0 = py0 - sc.film.halo;
-    const int full_w = sc.film.window[1] - sc.film.window[0];
-    const int sub_w = ra.window[1] - ra.window[0];
     const int pix = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int px = px0 + (pix & 7), py = py0 + (pix >> 3);
     // Native samples lie inside their pixel, so with a filter half-width <= 2 the footprint of every
@@ -725,13 +688,8 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra
     // in ra.image_xy.  Arbitrary replay records may belong anywhere and take the general path.)
     const bool fast5 = (!REPLAY || ra.image_xy != nullptr) && sc.film.wx <= 2.0f && sc.film.wy <= 2.0f;
     if (px < ra.window[1] && py < ra.window[3]) {
-        SampleSource src;
-        src.spp = ra.spp;
-        src.root = ra.root;
-        src.rec = nullptr;
-        const uint32_t pixel = static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0]));
-        src.pixel_key = nat_mix(ra.seed_key, pixel);
-        const uint32_t local_pixel = static_cast<uint32_t>((py - ra.window[2]) * sub_w + (px - ra.window[0]));
+        SampleSource src = camera_source<false>(sc, ra, px, py, 0u, nullptr);   // (the native law's; src.k and src.rec per sample)
+        const uint32_t local_pixel = window_pixel(ra, px, py);
         if (fast5) {
             float acc[25][4];
 #pragma unroll
@@ -746,10 +704,7 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra
                     image_x = xy[0];
                     image_y = xy[1];
                 } else {
-                    float u, v;
-                    src.native_2d(0u, 1u, 0u, false, &u, &v);
-                    image_x = px + u;
-                    image_y = py + v;
+                    image_position<false>(src, px, py, &image_x, &image_y);
                 }
                 const float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
                                                  static_cast<size_t>(local_pixel) * ra.spp + src.k);
@@ -801,16 +756,10 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra
                     const float* xy = ra.image_xy + 2 * (static_cast<size_t>(local_pixel) * ra.spp + k);
                     image_x = xy[0];
                     image_y = xy[1];
-                } else if (REPLAY) {
-                    const float* rec = ra.replay + (static_cast<size_t>(local_pixel) * ra.spp + k) * ra.dims;
-                    image_x = rec[0];
-                    image_y = rec[1];
                 } else {
                     src.k = k;
-                    float u, v;
-                    src.native_2d(0u, 1u, 0u, false, &u, &v);
-                    image_x = px + u;
-                    image_y = py + v;
+                    if (REPLAY) src.rec = ra.replay + (static_cast<size_t>(local_pixel) * ra.spp + k) * ra.dims;
+                    image_position<REPLAY>(src, px, py, &image_x, &image_y);
                 }
                 float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
                                            static_cast<size_t>(local_pixel) * ra.spp + k);

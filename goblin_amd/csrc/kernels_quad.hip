@@ -34,35 +34,25 @@ __global__ __launch_bounds__(GBL_BLOCK) void primary_kernel(DevScene sc, RenderA
     const uint32_t chunks = (static_cast<uint32_t>(ra.spp) + 63u) / 64u;
     const uint64_t n_tasks = static_cast<uint64_t>(ra.local_tiles) * 64u * chunks;   // (owned tile, pixel of the tile, 64-sample chunk)
     const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (GBL_BLOCK / 64);
-    const int sub_w = ra.window[1] - ra.window[0];
-    const int full_w = sc.film.window[1] - sc.film.window[0];
     for (uint64_t task = static_cast<uint64_t>(blockIdx.x) * (GBL_BLOCK / 64) + (threadIdx.x >> 6); task < n_tasks; task += waves) {
         const uint32_t c = static_cast<uint32_t>(task % chunks);
         const uint64_t pt = task / chunks;
         const uint32_t pix = static_cast<uint32_t>(pt % 64u), lt = static_cast<uint32_t>(pt / 64u);
-        const uint32_t tile = ra.shard_index + lt * ra.shard_count;
-        const int tx = tile % ra.tiles_x, ty = tile / ra.tiles_x;
-        const int px = ra.window[0] + GBL_TILE * tx + static_cast<int>(pix & 7u), py = ra.window[2] + GBL_TILE * ty + static_cast<int>(pix >> 3);
+        int px, py;
+        tile_pixel(ra, lt, pix, &px, &py);
         if (px >= ra.window[1] || py >= ra.window[3]) continue;   // (wave-uniform: an edge tile's clipped pixels)
         const uint32_t k = c * 64u + lane;
         const bool live = k < static_cast<uint32_t>(ra.spp);
-        SampleSource src;
-        src.spp = ra.spp;
-        src.root = ra.root;
-        src.rec = nullptr;
-        src.k = live ? k : 0u;
-        src.pixel_key = nat_mix(ra.seed_key, static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0])));
-        float u, v;
-        src.native_2d(0u, 1u, 0u, false, &u, &v);
+        float image_x, image_y;
         F3 o, d;
         float mint;
-        camera_ray<false>(sc.camera, px + u, py + v, 0.0f, 0.0f, &o, &d, &mint);
+        camera_sample<false, false>(sc, ra, px, py, live ? k : 0u, nullptr, &image_x, &image_y, &o, &d, &mint);
         Hit h;
         bool tied;
         packet_closest(sc, live, o, d, mint, wstack, h, tied);
         if (EXACT && live) tied = trace_needs_redo(sc, false, h.inst >= 0, h, tied, o, d, mint, INFINITY);
         if (live) {
-            const size_t out_index = static_cast<size_t>(static_cast<uint32_t>((py - ra.window[2]) * sub_w + (px - ra.window[0]))) * ra.spp + k;
+            const size_t out_index = static_cast<size_t>(window_pixel(ra, px, py)) * ra.spp + k;
             if (h.inst >= 0 && !tied) prim_hit[out_index] = make_float4(h.t, h.b1, h.b2, __uint_as_float(h.tri));
             prim_inst[out_index] = tied ? GBL_PRIM_TIED : h.inst;   // (a miss: GBL_PRIM_MISS)
             if (h.inst < 0 && !tied) {
