@@ -143,6 +143,11 @@ class gbl_timing(C.Structure):
     _fields_ = [("main_kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class gbl_develop_params(C.Structure):
+    _fields_ = [("bloom_radius", C.c_float), ("bloom_weight", C.c_float), ("tone_mapping", C.c_uint32),
+                ("reserved", C.c_uint32), ("stream", C.c_void_p)]
+
+
 class gbl_info(C.Structure):
     _fields_ = [("xres", C.c_int32), ("yres", C.c_int32), ("window", C.c_int32 * 4), ("blas_nodes", C.c_uint64),
                 ("tlas_nodes", C.c_uint64), ("triangles", C.c_uint64), ("instances", C.c_uint64),
@@ -153,10 +158,10 @@ class gbl_info(C.Structure):
 HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "gbl_host_free",
                 "gbl_host_last_error", "gbl_host_sample_window", "gbl_host_round_to_square",
                 "gbl_host_sample_dimension", "gbl_host_sample_dimension_scene", "gbl_host_film_normalize", "gbl_host_write_pfm", "gbl_host_output_path",
-                "gbl_host_bloom", "gbl_host_tone_map", "gbl_host_write_ppm", "gbl_host_write_exr", "gbl_host_write_image",
+                "gbl_host_bloom", "gbl_host_tone_map", "gbl_host_write_ppm", "gbl_host_write_ppm8", "gbl_host_write_exr", "gbl_host_write_image",
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_get_info", "gbl_destroy",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
 _host = None
@@ -194,6 +199,7 @@ def host_lib():
         lib.gbl_host_tone_map.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         lib.gbl_host_tone_map.restype = None
         lib.gbl_host_write_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
+        lib.gbl_host_write_ppm8.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
         lib.gbl_host_write_exr.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32]
         lib.gbl_host_write_image.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         lib.gbl_host_read_image.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -238,6 +244,7 @@ def hip_lib():
         lib.gbl_render.argtypes = [C.c_void_p, C.POINTER(gbl_render_params), C.c_void_p, C.POINTER(gbl_stats)]
         lib.gbl_film_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gbl_film_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gbl_film_develop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gbl_develop_params), C.c_void_p, C.c_void_p]
         lib.gbl_get_info.argtypes = [C.c_void_p, C.POINTER(gbl_info)]
         lib.gbl_get_timings.argtypes = [C.c_void_p, C.c_int, C.POINTER(gbl_timing)]
         lib.gbl_selftest_sincos.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]

@@ -663,7 +663,8 @@ void gbl_destroy(gbl_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (void* p : ctx->allocations) (void)hipFree(p);
-    for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill})
+    for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
+                       &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter})
         if (b->p) (void)hipFree(b->p);
     if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
     if (ctx->wf_ev_shade) (void)hipEventDestroy(ctx->wf_ev_shade);
@@ -1344,6 +1345,53 @@ static gbl_status gbl_film_resolve_impl(gbl_ctx* ctx, const float* film_accum, f
 }
 gbl_status gbl_film_resolve(gbl_ctx* ctx, const float* film_accum, float* rgb_out, void* stream) {
     return gbl_guard([&] { return gbl_film_resolve_impl(ctx, film_accum, rgb_out, stream); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+// Film::writeImage's tail (GoblinFilm.cpp:164-192 + Goblin::writeImage, GoblinImageIO.cpp:146-237) in passes on one stream:
+// normalise, bloom, tone map, quantise (kernels/develop.h).  Nothing comes back to the host.
+static gbl_status gbl_film_develop_impl(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* p, float* rgb_out, uint8_t* rgb8_out) {
+    if (!ctx || !film_accum || !p || (!rgb_out && !rgb8_out)) return GBL_ERR_INVALID;
+    if (rgb_out == film_accum) {
+        ctx->error = "gbl_film_develop: rgb_out may not alias film_accum";
+        return GBL_ERR_INVALID;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int width = ctx->info.xres, height = ctx->info.yres, n = width * height;
+    hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    gbl_status st;
+    float* rgb = rgb_out;
+    if (!rgb) {
+        if ((st = grow(ctx, ctx->dev_rgb, static_cast<uint64_t>(n) * 3 * sizeof(float), "developed image")) != GBL_OK) return st;
+        rgb = static_cast<float*>(ctx->dev_rgb.p);
+    }
+    int fw = 0;   // Goblin::bloom's filterWidth; 0 taps: nothing to do (as gbl_host_bloom)
+    if (p->bloom_radius > 0.0f && p->bloom_weight > 0.0f) fw = static_cast<int>(std::ceil(p->bloom_radius * std::max(width, height))) / 2;
+    if (fw > 0) {
+        const int fwx = std::min(fw, width), fwy = std::min(fw, height);
+        if ((st = grow(ctx, ctx->dev_rgb1, static_cast<uint64_t>(n) * 4 * sizeof(float), "normalised image")) != GBL_OK) return st;
+        if (ctx->dev_filter_fw != fw) {
+            ctx->dev_filter_fw = 0;
+            if ((st = grow(ctx, ctx->dev_filter, static_cast<uint64_t>(fwx) * fwy * sizeof(float), "bloom filter")) != GBL_OK) return st;
+            gbl_launch_bloom_filter(static_cast<float*>(ctx->dev_filter.p), fw, fwx, fwy, stream);
+            ctx->dev_filter_fw = fw;
+        }
+        gbl_launch_develop_resolve(film_accum, static_cast<float*>(ctx->dev_rgb1.p), n, stream);
+        gbl_launch_bloom(static_cast<const float*>(ctx->dev_rgb1.p), static_cast<const float*>(ctx->dev_filter.p), rgb, width, height, fw, fwx,
+                         p->bloom_weight, stream);
+    } else {
+        gbl_launch_film_resolve(film_accum, rgb, n, stream);
+    }
+    if (p->tone_mapping) {
+        if ((st = grow(ctx, ctx->dev_logs, (static_cast<uint64_t>(n) + 1) * sizeof(float), "tone map sums")) != GBL_OK) return st;
+        float* logs = static_cast<float*>(ctx->dev_logs.p);
+        gbl_launch_tone_map(rgb, logs, logs + n, n, stream);
+    }
+    if (rgb8_out) gbl_launch_quantize(rgb, rgb8_out, 3 * n, stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+gbl_status gbl_film_develop(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* params, float* rgb_out, uint8_t* rgb8_out) {
+    return gbl_guard([&] { return gbl_film_develop_impl(ctx, film_accum, params, rgb_out, rgb8_out); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 
 // ncclAllReduce(sum, float) over the film, resolved from librccl at first use so

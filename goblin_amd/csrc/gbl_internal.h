@@ -49,6 +49,12 @@ struct gbl_ctx {
     gbl_buf stream_xy;        // ... and the image position of every camera sample of the call (for the splat)
     gbl_buf wf_spill;         // the wavefront trace stacks' levels beyond LDS (wf_ensure_spill) ...
     int wf_spill_levels = 0;  // ... how many it holds
+    // gbl_film_develop's scratch (kernels/develop.h)
+    gbl_buf dev_rgb1;         // the normalised image as {r, g, b, 1} per pixel: what the bloom's windows and its blend read
+    gbl_buf dev_rgb;          // the developed image when the caller asks for bytes only
+    gbl_buf dev_logs;         // the tone map's logf(1e4 + luminance) per pixel, then 1 / Ywa^2 in one float after them
+    gbl_buf dev_filter;       // the bloom's filter table ...
+    int dev_filter_fw = 0;    // ... and the filter width it was built for (0: none yet)
     std::map<int, float> auto_rays_per_path;   // GBL_SCHEDULE_AUTO's pilot: rays per camera path by 2 * max_ray_depth + russian_roulette (gbl_render)
     double build_ms = 0.0;    // pack_scene + BVH construction + node / triangle upload
     // what gbl_update_instances needs to rebuild the TLAS
@@ -111,6 +117,12 @@ gbl_render_kernel gbl_kernel_vol(bool replay);
 void gbl_launch_vol_combine(float4* li, const float4* vol, uint64_t n, hipStream_t stream);
 void gbl_launch_tri_bounds_gather(const DevTri* tris, const DevTriBound* by_id, DevTriBound* out, uint32_t n);
 void gbl_launch_film_resolve(const float* accum, float* rgb, int n, hipStream_t stream);
+// ... and the passes of gbl_film_develop (kernels/develop.h)
+void gbl_launch_develop_resolve(const float* accum, float* rgb1, int n, hipStream_t stream);
+void gbl_launch_bloom_filter(float* filter, int fw, int fwx, int fwy, hipStream_t stream);
+void gbl_launch_bloom(const float* rgb1, const float* filter, float* out, int width, int height, int fw, int fwx, float weight, hipStream_t stream);
+void gbl_launch_tone_map(float* rgb, float* logs, float* inv, int n, hipStream_t stream);
+void gbl_launch_quantize(const float* rgb, uint8_t* rgb8, int n, hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

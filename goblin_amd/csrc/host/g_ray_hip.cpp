@@ -6,8 +6,9 @@
 // Stand-alone host with the call shape of the reference's g_ray
 // (/root/reference/src/g_ray.cpp:7-27): load the scene, render it, and run
 // Film::writeImage's tail (GoblinFilm.cpp:164-198): normalise, bloom, write the
-// film's "file" (default <scene>.exr, HALF B/G/R).  Everything goes through the C
-// ABI of include/goblin_hip.h.
+// film's "file" (default <scene>.exr, HALF B/G/R).  The tail runs on the device
+// (gbl_film_develop): a .ppm downloads bytes, .exr / .pfm the floats.  Everything
+// goes through the C ABI of include/goblin_hip.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -93,14 +94,40 @@ int main(int argc, char** argv) {
         fprintf(stderr, "gbl_render failed: %s\n", gbl_last_error(ctx));
         return 1;
     }
-    gbl_film_resolve(ctx, accum, rgb, nullptr);
     (void)hipDeviceSynchronize();
-    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    std::vector<float> host(npix * 3);
-    (void)hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDeviceToHost);
-    if (desc->film.bloom_radius > 0.0f && desc->film.bloom_weight > 0.0f)
-        gbl_host_bloom(host.data(), info.xres, info.yres, desc->film.bloom_radius, desc->film.bloom_weight);
-    if (gbl_host_write_image(out_path.c_str(), host.data(), info.xres, info.yres, static_cast<int32_t>(desc->film.tone_mapping)) != GBL_OK) {
+    double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // the render; developing the film is not in it
+    // Goblin::writeImage's dispatch (GoblinImageIO.cpp:146-167): .ppm is tone-mapped (when the film asks) and quantised,
+    // .exr (and .pfm) get the floats as they are, anything else becomes <name>.ppm without tone mapping
+    const size_t dot = out_path.rfind(".");
+    const std::string ext = dot == std::string::npos ? std::string() : out_path.substr(dot);
+    const bool is_ppm = ext == ".ppm" || ext == ".PPM";
+    const bool floats = ext == ".exr" || ext == ".EXR" || ext == ".pfm" || ext == ".PFM";
+    uint8_t* rgb8 = nullptr;
+    if (!floats && hipMalloc(reinterpret_cast<void**>(&rgb8), npix * 3) != hipSuccess) {
+        fprintf(stderr, "hipMalloc failed\n");
+        return 1;
+    }
+    gbl_develop_params dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.bloom_radius = desc->film.bloom_radius;
+    dp.bloom_weight = desc->film.bloom_weight;
+    dp.tone_mapping = is_ppm ? desc->film.tone_mapping : 0u;
+    if (gbl_film_develop(ctx, accum, &dp, floats ? rgb : nullptr, rgb8) != GBL_OK) {
+        fprintf(stderr, "gbl_film_develop failed: %s\n", gbl_last_error(ctx));
+        return 1;
+    }
+    (void)hipDeviceSynchronize();
+    gbl_status wst;
+    if (floats) {
+        std::vector<float> host(npix * 3);
+        (void)hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDeviceToHost);
+        wst = gbl_host_write_image(out_path.c_str(), host.data(), info.xres, info.yres, 0);
+    } else {
+        std::vector<uint8_t> host(npix * 3);
+        (void)hipMemcpy(host.data(), rgb8, host.size(), hipMemcpyDeviceToHost);
+        wst = gbl_host_write_ppm8((is_ppm ? out_path : out_path + ".ppm").c_str(), host.data(), info.xres, info.yres);
+    }
+    if (wst != GBL_OK) {
         fprintf(stderr, "write failed: %s\n", gbl_host_last_error());
         return 1;
     }
@@ -108,6 +135,7 @@ int main(int argc, char** argv) {
            static_cast<unsigned long long>(st.paths), sec, st.kernel_ms, st.paths / (st.kernel_ms * 1e3), out_path.c_str());
     (void)hipFree(accum);
     (void)hipFree(rgb);
+    if (rgb8) (void)hipFree(rgb8);
     gbl_destroy(ctx);
     gbl_host_free(hs);
     return 0;

@@ -3,7 +3,8 @@
 //   bloom            GoblinImageIO.cpp:169-218
 //   toneMapping      GoblinImageIO.cpp:220-236 (Reinhard '02 global operator as written there)
 //   writeImage       GoblinImageIO.cpp:146-167 (dispatch on the file extension)
-//   .ppm             GoblinImageIO.cpp:101-127 (ASCII P3, gamma 2.2)
+//   .ppm             GoblinImageIO.cpp:101-127 (ASCII P3, gamma 2.2); gbl_host_write_ppm8 writes the same text from bytes the
+//                    device has already quantised (gbl_film_develop)
 //   .exr             GoblinImageIO.cpp:35-98: three HALF channels B, G, R through tinyexr.  The reference links the
 //                    tinyexr copy that sits next to its sources; this writer emits the same OpenEXR 2.0 single-part
 //                    scanline layout with the same float->half rule (tinyexr.h:7164-7199: round half up on the 13
@@ -153,6 +154,19 @@ static gbl_status gbl_host_write_ppm_impl(const char* path, const float* rgb, in
 }
 gbl_status gbl_host_write_ppm(const char* path, const float* rgb, int32_t width, int32_t height) {
     return gbl_guard([&] { return gbl_host_write_ppm_impl(path, rgb, width, height); }, [](const std::string&) {});
+}
+
+static gbl_status gbl_host_write_ppm8_impl(const char* path, const uint8_t* rgb8, int32_t width, int32_t height) {
+    if (!path || !rgb8) return fail(GBL_ERR_INVALID, "null argument");
+    FILE* fp = fopen(path, "w");
+    if (!fp) return fail(GBL_ERR_IO, std::string("can not open file ") + path);
+    fprintf(fp, "P3\n%d %d\n%d\n", width, height, 255);
+    for (size_t i = 0; i < static_cast<size_t>(width) * height; ++i) fprintf(fp, "%d %d %d ", rgb8[3 * i], rgb8[3 * i + 1], rgb8[3 * i + 2]);
+    fclose(fp);
+    return GBL_OK;
+}
+gbl_status gbl_host_write_ppm8(const char* path, const uint8_t* rgb8, int32_t width, int32_t height) {
+    return gbl_guard([&] { return gbl_host_write_ppm8_impl(path, rgb8, width, height); }, [](const std::string&) {});
 }
 
 static gbl_status gbl_host_write_exr_impl(const char* path, const float* rgb, int32_t width, int32_t height) {

@@ -1,5 +1,6 @@
-// libgoblin_hip.so, kernel unit: the first-hit passes (subsurface term, participating medium), the film resolve, the
-// device BLAS build (kernels/lbvh.h) and the device self tests of the C ABI.
+// libgoblin_hip.so, kernel unit: the first-hit passes (subsurface term, participating medium), the film resolve and the
+// rest of Film::writeImage's tail (kernels/develop.h), the device BLAS build (kernels/lbvh.h) and the device self tests
+// of the C ABI.
 #include "abi_guard.h"
 #include <chrono>
 #include "gbl_internal.h"
@@ -7,6 +8,7 @@
 #include "kernels/subsurface.h"
 #include "kernels/volume.h"
 #include "kernels/lbvh.h"
+#include "kernels/develop.h"
 #include <hipcub/hipcub.hpp>
 
 #include <cstring>
@@ -47,6 +49,28 @@ __global__ void film_resolve_kernel(const float* accum, float* rgb, int n) {
 }
 void gbl_launch_film_resolve(const float* accum, float* rgb, int n, hipStream_t stream) {
     hipLaunchKernelGGL(film_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, accum, rgb, n);
+}
+
+// gbl_film_develop's passes (kernels/develop.h), each on `stream`
+void gbl_launch_develop_resolve(const float* accum, float* rgb1, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(develop_resolve_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const float4*>(accum),
+                       reinterpret_cast<float4*>(rgb1), n);
+}
+void gbl_launch_bloom_filter(float* filter, int fw, int fwx, int fwy, hipStream_t stream) {
+    hipLaunchKernelGGL(bloom_filter_kernel, dim3((fwx * fwy + 255) / 256), dim3(256), 0, stream, filter, fw, fwx, fwy);
+}
+void gbl_launch_bloom(const float* rgb1, const float* filter, float* out, int width, int height, int fw, int fwx, float weight, hipStream_t stream) {
+    const dim3 grid((width + GBL_BLOOM_TILE_W - 1) / GBL_BLOOM_TILE_W, (height + GBL_BLOOM_ROWS - 1) / GBL_BLOOM_ROWS);
+    hipLaunchKernelGGL(bloom_kernel, grid, dim3(64 * GBL_BLOOM_ROWS), 0, stream, reinterpret_cast<const float4*>(rgb1), filter, out, width, height,
+                       fw, fwx, weight);
+}
+void gbl_launch_tone_map(float* rgb, float* logs, float* inv, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(tone_log_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rgb, logs, n);
+    hipLaunchKernelGGL(tone_sum_kernel, dim3(1), dim3(GBL_TONE_THREADS), 0, stream, logs, n, inv);
+    hipLaunchKernelGGL(tone_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rgb, inv, n);
+}
+void gbl_launch_quantize(const float* rgb, uint8_t* rgb8, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(quantize_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rgb, rgb8, n);
 }
 
 // ---------------------------------------------------------------------------

@@ -109,6 +109,29 @@ class HipPathTracer:
     def new_film(self):
         return Film(self.info.xres, self.info.yres, self.device)
 
+    def develop(self, film, bloom_radius=None, bloom_weight=None, tone_mapping=None, want_rgb8=False):
+        """Film::writeImage's tail on the device (gbl_film_develop): normalise, bloom, tone map and, with want_rgb8, the
+        .ppm writer's 8-bit quantisation, on the current stream.  ``film`` is a Film or its (yres, xres, 4) accumulator
+        tensor; None for a setting means the scene's ``film`` block.
+        Returns {"rgb": (yres, xres, 3) float32 tensor, "rgb8": (yres, xres, 3) uint8 tensor or None}."""
+        torch = _torch()
+        accum = film.accum if isinstance(film, Film) else film
+        h, w = self.info.yres, self.info.xres
+        if tuple(accum.shape) != (h, w, 4) or accum.dtype != torch.float32 or accum.device != self.device or not accum.is_contiguous():
+            raise ValueError("film must be a contiguous (%d, %d, 4) float32 tensor on %s" % (h, w, self.device))
+        f = self.scene.desc.film
+        p = _abi.gbl_develop_params()
+        p.bloom_radius = f.bloom_radius if bloom_radius is None else float(bloom_radius)
+        p.bloom_weight = f.bloom_weight if bloom_weight is None else float(bloom_weight)
+        p.tone_mapping = f.tone_mapping if tone_mapping is None else (1 if tone_mapping else 0)
+        p.stream = torch.cuda.current_stream(self.device).cuda_stream
+        rgb = torch.empty((h, w, 3), dtype=torch.float32, device=self.device)
+        rgb8 = torch.empty((h, w, 3), dtype=torch.uint8, device=self.device) if want_rgb8 else None
+        st = self.lib.gbl_film_develop(self.handle, accum.data_ptr(), C.byref(p), rgb.data_ptr(), rgb8.data_ptr() if want_rgb8 else None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return {"rgb": rgb, "rgb8": rgb8}
+
     def _params(self, setting=None, window=None, seed=0, replay=None, li_out=None, stats=False, rr=False, shard=None,
                 schedule=0, sampler="native", exact_ties=False):
         s = setting or self.scene.desc.setting

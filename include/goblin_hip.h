@@ -238,7 +238,8 @@ typedef struct gbl_film {
     float filter_width[2];
     float gaussian_falloff;
     float mitchell_b, mitchell_c;
-    /* Film::writeImage post-processing (GoblinFilm.cpp:164-198, 212-215); host side only */
+    /* Film::writeImage post-processing (GoblinFilm.cpp:164-198, 212-215): applied by whoever develops the film --
+     * gbl_film_develop on the device, or gbl_host_bloom / gbl_host_tone_map on the host; gbl_render ignores them */
     uint32_t tone_mapping;
     float bloom_radius, bloom_weight;
 } gbl_film;
@@ -362,6 +363,9 @@ void gbl_host_bloom(float* rgb, int32_t xres, int32_t yres, float bloom_radius, 
 void gbl_host_tone_map(float* rgb, int32_t xres, int32_t yres);
 /* writeImagePPM (GoblinImageIO.cpp:101-127): ASCII P3, gamma 2.2. */
 gbl_status gbl_host_write_ppm(const char* path, const float* rgb, int32_t xres, int32_t yres);
+/* The same file from bytes that are already quantised (gbl_film_develop's rgb8_out): W*H*3 values, the ASCII P3 text of
+ * writeImagePPM. */
+gbl_status gbl_host_write_ppm8(const char* path, const uint8_t* rgb8, int32_t xres, int32_t yres);
 /* writeImageEXR (GoblinImageIO.cpp:35-98): HALF channels B, G, R with tinyexr's
  * float->half rounding; scanlines are stored uncompressed (tinyexr defaults to
  * ZIP), so the pixels are the reference's, the bytes are not. */
@@ -495,6 +499,24 @@ gbl_status gbl_film_allreduce(gbl_ctx* ctx, void* rccl_comm, float* film_accum, 
 
 /* Device-side Film::writeImage normalise: rgb_out[W*H*3] = rgb / weight. */
 gbl_status gbl_film_resolve(gbl_ctx* ctx, const float* film_accum, float* rgb_out, void* stream);
+
+typedef struct gbl_develop_params {
+    float bloom_radius, bloom_weight; /* either <= 0: no bloom (GoblinFilm.cpp:188) */
+    uint32_t tone_mapping;            /* Goblin::toneMapping before the outputs are written */
+    uint32_t reserved;
+    void* stream;                     /* hipStream_t, NULL = default stream */
+} gbl_develop_params;
+
+/* Film::writeImage's tail on the device: rgb = accum.rgb * (1 / accum.w) exactly as gbl_film_resolve,
+ * then Goblin::bloom, then (tone_mapping) Goblin::toneMapping.  rgb_out: W*H*3 floats, or NULL.
+ * rgb8_out: W*H*3 bytes = writeImagePPM's int(clamp(powf(c, 1/2.2f), 0, 1) * 255), or NULL.
+ * Asynchronous on params->stream; scratch lives in the context.
+ * Both are device pointers; one of them may be NULL, rgb_out may not alias film_accum.  The pixels are the reference's bit
+ * for bit (glibc's powf / logf / expf restated for the device, the reference's order in every sum).  The scratch and the
+ * cached bloom filter table belong to the context: calls that share a context are ordered by the caller, on one stream or
+ * by events.  Pixels of weight 0 and negative or non-finite values are unspecified, as for gbl_host_write_ppm. */
+gbl_status gbl_film_develop(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* params,
+                            float* rgb_out, uint8_t* rgb8_out);
 
 /* Device time of recent gbl_render calls, from HIP events recorded on the render stream
  * around the dominant kernel and around the whole call (no host synchronisation happens
