@@ -148,6 +148,16 @@ class gbl_develop_params(C.Structure):
                 ("reserved", C.c_uint32), ("stream", C.c_void_p)]
 
 
+class gbl_aov_sample(C.Structure):
+    _fields_ = [("albedo", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("instance", C.c_int32),
+                ("position", C.c_float * 3), ("hit", C.c_uint32)]
+
+
+class gbl_aov_targets(C.Structure):
+    _fields_ = [("albedo_accum", C.c_void_p), ("normal_accum", C.c_void_p), ("depth_accum", C.c_void_p),
+                ("samples_out", C.c_void_p)]
+
+
 class gbl_info(C.Structure):
     _fields_ = [("xres", C.c_int32), ("yres", C.c_int32), ("window", C.c_int32 * 4), ("blas_nodes", C.c_uint64),
                 ("tlas_nodes", C.c_uint64), ("triangles", C.c_uint64), ("instances", C.c_uint64),
@@ -161,7 +171,8 @@ HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "
                 "gbl_host_bloom", "gbl_host_tone_map", "gbl_host_write_ppm", "gbl_host_write_ppm8", "gbl_host_write_exr", "gbl_host_write_image",
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_get_info", "gbl_destroy",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
+               "gbl_aov_resolve_depth", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
 _host = None
@@ -245,6 +256,8 @@ def hip_lib():
         lib.gbl_film_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gbl_film_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gbl_film_develop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(gbl_develop_params), C.c_void_p, C.c_void_p]
+        lib.gbl_render_aov.argtypes = [C.c_void_p, C.POINTER(gbl_render_params), C.POINTER(gbl_aov_targets), C.POINTER(gbl_stats)]
+        lib.gbl_aov_resolve_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gbl_get_info.argtypes = [C.c_void_p, C.POINTER(gbl_info)]
         lib.gbl_get_timings.argtypes = [C.c_void_p, C.c_int, C.POINTER(gbl_timing)]
         lib.gbl_selftest_sincos.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]

@@ -663,7 +663,7 @@ void gbl_destroy(gbl_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (void* p : ctx->allocations) (void)hipFree(p);
-    for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
+    for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->aov, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
                        &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter})
         if (b->p) (void)hipFree(b->p);
     if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
@@ -1311,6 +1311,158 @@ gbl_status gbl_render_impl(gbl_ctx* ctx, const gbl_render_params* p, float* film
     return finish_render(ctx, pl, knobs, tev, stream, stats);
 }
 
+// ---------------------------------------------------------------------------
+// gbl_render_aov: the first-hit feature pass (kernels/aov.h) and one wf_splat per requested film, a chunk of the samples per
+// pixel at a time.  Its plan is the part of plan_render that describes the camera samples of a call -- window, tiles, shard,
+// sample layout, seed -- and none of the integrators' checks and budgets.
+// ---------------------------------------------------------------------------
+struct AovKnobs {
+    bool packet;     // GBL_AOV_PACKET=0: one ray per lane also where the packet kernel applies (A/B, bit-identity test)
+    int pass_spp;    // GBL_AOV_PASS_SPP: at most this many samples per pixel per chunk (tests: force several chunks); 0: the budget's
+};
+AovKnobs read_aov_knobs() {
+    AovKnobs k;
+    const char* e = getenv("GBL_AOV_PACKET");
+    k.packet = e == nullptr || e[0] != '0';
+    e = getenv("GBL_AOV_PASS_SPP");
+    k.pass_spp = e ? std::max(0, atoi(e)) : 0;
+    return k;
+}
+
+gbl_status plan_aov(gbl_ctx* ctx, const gbl_render_params* p, Plan* pl) {
+    const DevScene& sc = ctx->scene;
+    RenderArgs& ra = pl->ra;
+    memset(&ra, 0, sizeof(ra));
+    if (p->integrator != GBL_INTEGRATOR_PATH && p->integrator != GBL_INTEGRATOR_AO && p->integrator != GBL_INTEGRATOR_WHITTED)
+        return fail(ctx, GBL_ERR_INVALID, "unknown integrator");
+    if (p->sample_per_pixel < 1 || p->max_ray_depth < 1) return fail(ctx, GBL_ERR_INVALID, "sample_per_pixel and max_ray_depth must be >= 1");
+    if (p->sample_mode == GBL_SAMPLES_STREAM)
+        return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_render_aov: the image positions of GBL_SAMPLES_STREAM depend on the draws Li makes");
+    if (p->sample_mode != GBL_SAMPLES_REPLAY && p->sample_mode != GBL_SAMPLES_NATIVE) return fail(ctx, GBL_ERR_INVALID, "unknown sample_mode");
+    if (p->sample_mode == GBL_SAMPLES_REPLAY && !p->replay_samples) return fail(ctx, GBL_ERR_INVALID, "replay mode needs replay_samples");
+    sample_layout(sc, p, ra);   // (the integrator and depth fields only size the replay record)
+    const int32_t* full = sc.film.window;
+    const bool whole = p->window[0] == 0 && p->window[1] == 0 && p->window[2] == 0 && p->window[3] == 0;
+    for (int i = 0; i < 4; ++i) ra.window[i] = whole ? full[i] : p->window[i];
+    if (ra.window[0] < full[0] || ra.window[1] > full[1] || ra.window[2] < full[2] || ra.window[3] > full[3] ||
+        ra.window[0] > ra.window[1] || ra.window[2] > ra.window[3])
+        return fail(ctx, GBL_ERR_INVALID, "render window lies outside the film's sample window");
+    pl->npix = static_cast<uint64_t>(ra.window[1] - ra.window[0]) * (ra.window[3] - ra.window[2]);
+    if (pl->npix * ra.spp >= (1ull << 32)) return fail(ctx, GBL_ERR_INVALID, "more than 2^32 camera samples in one call: split the window");
+    pl->entries = pl->npix * ra.spp;
+    ra.tiles_x = (ra.window[1] - ra.window[0] + GBL_TILE - 1) / GBL_TILE;
+    ra.tiles_y = (ra.window[3] - ra.window[2] + GBL_TILE - 1) / GBL_TILE;
+    ra.shard_count = std::max(1, p->tile_shard_count);
+    ra.shard_index = p->tile_shard_count > 1 ? p->tile_shard_index : 0;
+    if (ra.shard_index < 0 || ra.shard_index >= ra.shard_count) return fail(ctx, GBL_ERR_INVALID, "tile_shard_index out of range");
+    pl->total_tiles = ra.tiles_x * ra.tiles_y;
+    ra.local_tiles = pl->total_tiles > ra.shard_index ? (pl->total_tiles - ra.shard_index + ra.shard_count - 1) / ra.shard_count : 0;
+    ra.chunks = 1;
+    ra.chunk_spp = ra.spp;
+    ra.seed_key = host_mix(static_cast<uint32_t>(p->seed), static_cast<uint32_t>(p->seed >> 32));
+    ra.replay = p->replay_samples;
+    ra.work_counter = ctx->work_counter;
+    ra.stats = ctx->stats;
+    pl->replay = p->sample_mode == GBL_SAMPLES_REPLAY;
+    pl->want_stats = p->collect_stats != 0;
+    if (stack_lds_bytes(sc) > 160 * 1024) return fail(ctx, GBL_ERR_UNSUPPORTED, "scene's BVH is too deep for the LDS traversal stacks");
+    return GBL_OK;
+}
+
+gbl_status gbl_render_aov_impl(gbl_ctx* ctx, const gbl_render_params* p, const gbl_aov_targets* tg, gbl_stats* stats, const AovKnobs& knobs) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!p || !tg) return fail(ctx, GBL_ERR_INVALID, "null argument");
+    if (!tg->albedo_accum && !tg->normal_accum && !tg->depth_accum && !tg->samples_out)
+        return fail(ctx, GBL_ERR_INVALID, "gbl_render_aov: every target is NULL");
+    Plan pl;
+    gbl_status st = plan_aov(ctx, p, &pl);
+    if (st != GBL_OK) return st;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (pl.ra.local_tiles == 0 || pl.entries == 0) return GBL_OK;
+    const DevScene& sc = ctx->scene;
+    RenderArgs ra = pl.ra;
+    hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (pl.want_stats) HIP_TRY(ctx, hipMemsetAsync(ctx->stats, 0, 32 * sizeof(unsigned long long), stream));
+
+    // a chunk's planes: 16 bytes per sample and requested film, inside the per-sample budget gbl_render keeps to
+    float* const films[3] = {tg->albedo_accum, tg->normal_accum, tg->depth_accum};
+    const int n_films = (films[0] ? 1 : 0) + (films[1] ? 1 : 0) + (films[2] ? 1 : 0);
+    int pass_spp = ra.spp;
+    if (n_films > 0) {
+        const uint64_t per_spp = pl.npix * sizeof(float4) * n_films;
+        pass_spp = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(ra.spp, li_budget_bytes(ctx) / per_spp)));
+    }
+    if (knobs.pass_spp > 0) pass_spp = std::min(pass_spp, knobs.pass_spp);
+    float4* planes[3] = {nullptr, nullptr, nullptr};
+    if (n_films > 0) {
+        const uint64_t plane = pl.npix * static_cast<uint64_t>(pass_spp);
+        if ((st = grow(ctx, ctx->aov, plane * sizeof(float4) * n_films, "feature planes")) != GBL_OK) return st;
+        float4* q = static_cast<float4*>(ctx->aov.p);
+        for (int f = 0; f < 3; ++f)
+            if (films[f]) {
+                planes[f] = q;
+                q += plane;
+            }
+    }
+    // Kernel: packets for the lean scenes under the native sampler (see aov_packet_kernel), one ray per lane otherwise.  The
+    // EXT build wherever gbl_render takes one -- feature scenes, replay, instrumented calls -- and with it the tie rule.
+    const bool ext = sc.extended != 0 || pl.replay || pl.want_stats;
+    const bool packet = !ext && knobs.packet && sc.stack_entries <= 64;   // (kernels/packet.h GBL_PACKET_STACK, as primary_pass)
+    gbl_aov_kernel kernel = packet ? gbl_kernel_aov_packet(p->exact_ties != 0) : gbl_kernel_aov(pl.replay, pl.want_stats, ext, p->exact_ties != 0);
+    const size_t lds = stack_lds_bytes(sc);
+    if ((st = allow_lds(ctx, kernel, lds + (packet ? 4096 : 0))) != GBL_OK) return st;   // (the packet kernel's static 3 KB count against the same limit)
+    gbl_wf_kernel k_splat = gbl_kernel_wf_splat(pl.replay, pl.want_stats);
+    if (stats) HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));
+    for (int k0 = 0; k0 < ra.spp; k0 += pass_spp) {
+        AovArgs aa;
+        aa.albedo = planes[0];
+        aa.normal = planes[1];
+        aa.depth = planes[2];
+        aa.samples = tg->samples_out;
+        aa.pass_k0 = k0;
+        aa.pass_spp = std::min(pass_spp, ra.spp - k0);
+        const uint64_t threads = packet ? static_cast<uint64_t>(ra.local_tiles) * 64 * ((aa.pass_spp + 63) / 64) * 64
+                                        : static_cast<uint64_t>(ra.local_tiles) * 64 * aa.pass_spp;
+        const uint64_t cap = static_cast<uint64_t>(ctx->num_cus) * (packet ? 64 : 8);   // grid-stride (the primary pass's grid: 64 workgroups per CU)
+        const dim3 grid(static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>((threads + GBL_BLOCK - 1) / GBL_BLOCK, cap))));
+        hipLaunchKernelGGL(kernel, grid, dim3(GBL_BLOCK), lds, stream, sc, ra, aa);
+        HIP_TRY(ctx, hipGetLastError());
+        WfArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        wa.pass_k0 = k0;
+        wa.pass_spp = aa.pass_spp;
+        for (int f = 0; f < 3; ++f) {
+            if (!films[f]) continue;
+            ra.film = films[f];
+            wa.li_buf = planes[f];
+            hipLaunchKernelGGL(k_splat, dim3(ra.local_tiles), dim3(GBL_BLOCK), tile_lds_bytes(sc), stream, sc, ra, wa);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    if (!stats) return GBL_OK;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    stats->kernel_ms = ms;
+    uint64_t shard_pixels = 0;
+    for (int t = ra.shard_index; t < pl.total_tiles; t += ra.shard_count) {
+        const int tx = t % ra.tiles_x, ty = t / ra.tiles_x;
+        shard_pixels += static_cast<uint64_t>(std::min(GBL_TILE, ra.window[1] - (ra.window[0] + GBL_TILE * tx))) *
+                        std::min(GBL_TILE, ra.window[3] - (ra.window[2] + GBL_TILE * ty));
+    }
+    stats->paths = stats->extension_rays = shard_pixels * ra.spp;
+    if (pl.want_stats) {
+        unsigned long long h[32];
+        HIP_TRY(ctx, hipMemcpy(h, ctx->stats, sizeof(h), hipMemcpyDeviceToHost));
+        stats->nodes = h[3];
+        stats->tris = h[4];
+        stats->splats = h[5];
+    }
+    return GBL_OK;
+}
+
 }   // namespace
 
 extern "C" {
@@ -1392,6 +1544,21 @@ static gbl_status gbl_film_develop_impl(gbl_ctx* ctx, const float* film_accum, c
 }
 gbl_status gbl_film_develop(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* params, float* rgb_out, uint8_t* rgb8_out) {
     return gbl_guard([&] { return gbl_film_develop_impl(ctx, film_accum, params, rgb_out, rgb8_out); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+gbl_status gbl_render_aov(gbl_ctx* ctx, const gbl_render_params* params, const gbl_aov_targets* targets, gbl_stats* stats) {
+    return gbl_guard([&] { return gbl_render_aov_impl(ctx, params, targets, stats, read_aov_knobs()); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+static gbl_status gbl_aov_resolve_depth_impl(gbl_ctx* ctx, const float* depth_accum, float* depth_out, float* coverage_out, void* stream) {
+    if (!ctx || !depth_accum || !depth_out) return GBL_ERR_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gbl_launch_aov_resolve_depth(depth_accum, depth_out, coverage_out, ctx->info.xres * ctx->info.yres, static_cast<hipStream_t>(stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+gbl_status gbl_aov_resolve_depth(gbl_ctx* ctx, const float* depth_accum, float* depth_out, float* coverage_out, void* stream) {
+    return gbl_guard([&] { return gbl_aov_resolve_depth_impl(ctx, depth_accum, depth_out, coverage_out, stream); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 
 // ncclAllReduce(sum, float) over the film, resolved from librccl at first use so

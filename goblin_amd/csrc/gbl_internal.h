@@ -13,6 +13,7 @@
 #include "../../include/goblin_hip.h"
 #include "device_scene.h"
 #include "kernels/wf_args.h"
+#include "kernels/aov_args.h"
 
 // A device buffer of the context, grown on demand (gbl_api.hip grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -45,6 +46,7 @@ struct gbl_ctx {
     gbl_buf prim_items;       // ... and its word per work item of the path kernel (RenderArgs::prim_items)
     gbl_buf vol;              // per-sample {transmittance, Lv} (scenes with a participating medium)
     gbl_buf sss;              // per-sample Lsubsurface (scenes with subsurface materials)
+    gbl_buf aov;              // gbl_render_aov: a chunk's per-sample feature planes (float4 each, up to three)
     gbl_buf stream_scratch;   // GBL_SAMPLES_STREAM: the workgroups' sample-generation scratch ...
     gbl_buf stream_xy;        // ... and the image position of every camera sample of the call (for the splat)
     gbl_buf wf_spill;         // the wavefront trace stacks' levels beyond LDS (wf_ensure_spill) ...
@@ -90,6 +92,7 @@ struct gbl_ctx {
 typedef void (*gbl_render_kernel)(DevScene, RenderArgs);
 typedef void (*gbl_wf_kernel)(DevScene, RenderArgs, WfArgs);
 typedef void (*gbl_li_kernel)(DevScene, RenderArgs, float4*);
+typedef void (*gbl_aov_kernel)(DevScene, RenderArgs, AovArgs);
 
 // kernels_path.hip: the persistent megakernel and the AO kernel (kernels/render_kernels.h), native / replay samplers
 gbl_render_kernel gbl_kernel_path(bool replay, bool stats, bool ext, bool exact_ties = false);
@@ -123,6 +126,11 @@ void gbl_launch_bloom_filter(float* filter, int fw, int fwx, int fwy, hipStream_
 void gbl_launch_bloom(const float* rgb1, const float* filter, float* out, int width, int height, int fw, int fwx, float weight, hipStream_t stream);
 void gbl_launch_tone_map(float* rgb, float* logs, float* inv, int n, hipStream_t stream);
 void gbl_launch_quantize(const float* rgb, uint8_t* rgb8, int n, hipStream_t stream);
+// kernels_aov.hip: the first-hit feature pass of gbl_render_aov (kernels/aov.h), one lane per camera sample or, for the lean
+// scenes under the native sampler, one packet per pixel; and the depth film's resolve
+gbl_aov_kernel gbl_kernel_aov(bool replay, bool stats, bool ext, bool exact_ties);
+gbl_aov_kernel gbl_kernel_aov_packet(bool exact_ties);
+void gbl_launch_aov_resolve_depth(const float* accum, float* depth, float* coverage, int n, hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

@@ -1,4 +1,8 @@
-// g_ray_hip <scene.json> [--device N] [--seed S] [--sampler native|stream] [--out file.{exr,ppm,pfm}]
+// g_ray_hip <scene.json> [--device N] [--seed S] [--sampler native|stream] [--out file.{exr,ppm,pfm}] [--aov]
+//
+// --aov also writes the first-hit feature films (gbl_render_aov) of the same camera samples beside the image:
+// <output stem>.albedo.pfm, .normal.pfm (both normalised) and .depth.pfm (r = depth, g = coverage, b = 0).  Portable float
+// maps are lossless; the EXR writer stores halves and would quantise depth.  Native sampler only.
 //
 // --sampler stream renders with the reference's own sample stream (GBL_SAMPLES_STREAM): the image is the one the
 // reference binary writes for this scene file, up to float summation order; native (default) is the fast sampler.
@@ -23,18 +27,28 @@
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "Usage: g_ray_hip scene_file.json [--device N] [--seed S] [--sampler native|stream] [--out image.{exr,ppm,pfm}]\n");
+        fprintf(stderr, "Usage: g_ray_hip scene_file.json [--device N] [--seed S] [--sampler native|stream] [--out image.{exr,ppm,pfm}] [--aov]\n");
         return 0;
     }
     std::string scene_path = argv[1], out_path;
     int device = 0;
     unsigned long long seed = 0;
-    bool stream_sampler = false;
-    for (int i = 2; i + 1 < argc; i += 2) {
+    bool stream_sampler = false, aov = false;
+    for (int i = 2; i < argc; i += 2) {
+        if (!strcmp(argv[i], "--aov")) {   // (the one switch without a value)
+            aov = true;
+            i -= 1;
+            continue;
+        }
+        if (i + 1 >= argc) break;
         if (!strcmp(argv[i], "--device")) device = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--seed")) seed = strtoull(argv[i + 1], nullptr, 10);
         else if (!strcmp(argv[i], "--out")) out_path = argv[i + 1];
         else if (!strcmp(argv[i], "--sampler")) stream_sampler = !strcmp(argv[i + 1], "stream");
+    }
+    if (aov && stream_sampler) {   // (gbl_render_aov refuses GBL_SAMPLES_STREAM: say so before rendering anything)
+        fprintf(stderr, "--aov needs the native sampler\n");
+        return 1;
     }
     gbl_host_scene* hs = nullptr;
     if (gbl_host_load_file(scene_path.c_str(), &hs) != GBL_OK) {
@@ -96,6 +110,59 @@ int main(int argc, char** argv) {
     }
     (void)hipDeviceSynchronize();
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();   // the render; developing the film is not in it
+    if (aov) {
+        // the three feature films of the very samples rendered above, resolved on the device, written as portable float maps
+        float* feat = nullptr;   // 3 accumulators, then depth and coverage
+        if (hipMalloc(reinterpret_cast<void**>(&feat), npix * 14 * sizeof(float)) != hipSuccess) {
+            fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        (void)hipMemset(feat, 0, npix * 12 * sizeof(float));
+        gbl_aov_targets tg;
+        memset(&tg, 0, sizeof(tg));
+        tg.albedo_accum = feat;
+        tg.normal_accum = feat + 4 * npix;
+        tg.depth_accum = feat + 8 * npix;
+        gbl_render_params ap = p;
+        ap.li_out = nullptr;
+        memset(ap.window, 0, sizeof(ap.window));
+        if (gbl_render_aov(ctx, &ap, &tg, nullptr) != GBL_OK) {
+            fprintf(stderr, "gbl_render_aov failed: %s\n", gbl_last_error(ctx));
+            return 1;
+        }
+        const size_t dot_a = out_path.rfind("."), slash = out_path.rfind("/");
+        const std::string stem = (dot_a == std::string::npos || (slash != std::string::npos && dot_a < slash)) ? out_path : out_path.substr(0, dot_a);
+        std::vector<float> host(npix * 3), dc(npix * 2);
+        float* const films[2] = {tg.albedo_accum, tg.normal_accum};
+        const char* const names[2] = {".albedo.pfm", ".normal.pfm"};
+        for (int f = 0; f < 2; ++f) {
+            if (gbl_film_resolve(ctx, films[f], rgb, nullptr) != GBL_OK) {
+                fprintf(stderr, "gbl_film_resolve failed: %s\n", gbl_last_error(ctx));
+                return 1;
+            }
+            (void)hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDeviceToHost);
+            if (gbl_host_write_pfm((stem + names[f]).c_str(), host.data(), info.xres, info.yres) != GBL_OK) {
+                fprintf(stderr, "write failed: %s\n", gbl_host_last_error());
+                return 1;
+            }
+        }
+        if (gbl_aov_resolve_depth(ctx, tg.depth_accum, feat + 12 * npix, feat + 13 * npix, nullptr) != GBL_OK) {
+            fprintf(stderr, "gbl_aov_resolve_depth failed: %s\n", gbl_last_error(ctx));
+            return 1;
+        }
+        (void)hipMemcpy(dc.data(), feat + 12 * npix, dc.size() * sizeof(float), hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < npix; ++i) {
+            host[3 * i] = dc[i];
+            host[3 * i + 1] = dc[npix + i];
+            host[3 * i + 2] = 0.0f;
+        }
+        if (gbl_host_write_pfm((stem + ".depth.pfm").c_str(), host.data(), info.xres, info.yres) != GBL_OK) {
+            fprintf(stderr, "write failed: %s\n", gbl_host_last_error());
+            return 1;
+        }
+        printf("write feature films to : %s.{albedo,normal,depth}.pfm\n", stem.c_str());
+        (void)hipFree(feat);
+    }
     // Goblin::writeImage's dispatch (GoblinImageIO.cpp:146-167): .ppm is tone-mapped (when the film asks) and quantised,
     // .exr (and .pfm) get the floats as they are, anything else becomes <name>.ppm without tone mapping
     const size_t dot = out_path.rfind(".");

@@ -192,3 +192,65 @@ class HipPathTracer:
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return {"film": film, "li": li, "stats": st_out.as_dict() if st_out else None, "paths": npaths}
+
+    def render_aov(self, albedo=True, normal=True, depth=True, want_samples=False, films=None, setting=None, window=None,
+                   seed=0, replay_samples=None, shard=None, exact_ties=False, stats=False, sampler="native", timed=False):
+        """First-hit feature films of the camera samples ``render`` draws for the same arguments (gbl_render_aov).
+
+        albedo / normal / depth: which films to produce; ``films`` may carry existing ones ({"albedo": Film, ...}), which are
+        accumulated into.  want_samples: also the per-sample records, an (n, 12) float32 tensor in ``render``'s li order --
+        {albedo(3), t, normal(3), instance, position(3), hit}; words 7 and 11 are integers, ``samples_i32`` is the int32 view.
+        The depth film holds {sum w*t*hit, sum w*hit, 0, sum w}: see ``resolve_depth``.
+        stats: gbl_stats with the node / triangle counters (the instrumented kernels); timed: gbl_stats for its kernel_ms only.
+        Returns dict(albedo=, normal=, depth= Film or None, samples=, samples_i32=, stats=, paths=).
+        """
+        torch = _torch()
+        films = dict(films or {})
+        out = {}
+        for name, want in (("albedo", albedo), ("normal", normal), ("depth", depth)):
+            f = films.get(name)
+            out[name] = f if f is not None else (self.new_film() if want else None)
+        replay = None
+        if replay_samples is not None:
+            replay = torch.as_tensor(np.ascontiguousarray(replay_samples, np.float32) if isinstance(
+                replay_samples, np.ndarray) else replay_samples, dtype=torch.float32, device=self.device).contiguous()
+        s = setting or self.scene.desc.setting
+        w = window or self.window
+        spp = _abi.host_lib().gbl_host_round_to_square(s.sample_per_pixel)
+        npaths = (w[1] - w[0]) * (w[3] - w[2]) * spp
+        if replay is not None:
+            dims = _abi.host_lib().gbl_host_sample_dimension_scene(C.byref(self.scene.desc), C.byref(s))
+            if tuple(replay.shape) != (npaths, dims):
+                raise ValueError("replay_samples must have shape (%d, %d), got %s" % (npaths, dims, tuple(replay.shape)))
+        samples = torch.zeros((npaths, 12), dtype=torch.float32, device=self.device) if want_samples else None
+        p = self._params(s, window, seed, replay, None, stats, False, shard, 0, sampler, exact_ties)
+        if sampler == "replay" and replay is None:
+            p.sample_mode = _abi.GBL_SAMPLES_REPLAY
+        tg = _abi.gbl_aov_targets()
+        tg.albedo_accum = out["albedo"].accum.data_ptr() if out["albedo"] is not None else None
+        tg.normal_accum = out["normal"].accum.data_ptr() if out["normal"] is not None else None
+        tg.depth_accum = out["depth"].accum.data_ptr() if out["depth"] is not None else None
+        tg.samples_out = samples.data_ptr() if samples is not None else None
+        st_out = _abi.gbl_stats() if (stats or timed) else None
+        st = self.lib.gbl_render_aov(self.handle, C.byref(p), C.byref(tg), C.byref(st_out) if st_out else None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        out.update(samples=samples, samples_i32=samples.view(torch.int32) if samples is not None else None,
+                   stats=st_out.as_dict() if st_out else None, paths=npaths)
+        return out
+
+    def resolve_depth(self, film):
+        """(depth, coverage) of a depth film (gbl_aov_resolve_depth) on the current stream: two (yres, xres) float32 tensors,
+        depth = x / y and coverage = y / w of the accumulator, 0 where the denominator is 0."""
+        torch = _torch()
+        accum = film.accum if isinstance(film, Film) else film
+        h, w = self.info.yres, self.info.xres
+        if tuple(accum.shape) != (h, w, 4) or accum.dtype != torch.float32 or accum.device != self.device or not accum.is_contiguous():
+            raise ValueError("film must be a contiguous (%d, %d, 4) float32 tensor on %s" % (h, w, self.device))
+        depth = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        coverage = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        st = self.lib.gbl_aov_resolve_depth(self.handle, accum.data_ptr(), depth.data_ptr(), coverage.data_ptr(),
+                                            torch.cuda.current_stream(self.device).cuda_stream)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return depth, coverage

@@ -518,6 +518,38 @@ typedef struct gbl_develop_params {
 gbl_status gbl_film_develop(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* params,
                             float* rgb_out, uint8_t* rgb8_out);
 
+/* First-hit features of the camera samples.  Camera sample i is the one gbl_render draws for the same
+ * params (sample_mode, seed, sample_per_pixel, window, tile shard, and the integrator / depth fields that size a replay
+ * record): record i here and entry i of li_out describe the same camera ray.  The ray is traced as Scene::intersect does it --
+ * unfiltered closest hit, mint from the camera, Material::perturb on the fragment (GoblinScene.cpp:75-83); exact_ties as in
+ * gbl_render.  A miss leaves hit = 0, t = -1, instance = -1 and zeros. */
+typedef struct gbl_aov_sample {      /* 48 bytes */
+    float albedo[3];   /* the material's first colour slot as the bounce-0 BSDF reads it: Lambert Kd, Blinn Kg, transparent /
+                        * mirror Kr (color / tex_color), subsurface Kr (color3 / tex_color3), a mask's wrapped material's;
+                        * texture lookups see the camera ray's differentials (computeUVDifferential, GoblinPathtracer.cpp:77) */
+    float t;           /* the ray parameter of the hit (ray.maxt after the query) */
+    float normal[3];   /* world-space shading normal after perturb, NOT flipped towards the viewer */
+    int32_t instance;  /* index into gbl_scene_desc.instances */
+    float position[3]; /* the fragment's world position */
+    uint32_t hit;
+} gbl_aov_sample;
+typedef struct gbl_aov_targets {     /* device pointers; any may be NULL, not all */
+    /* films of xres*yres float4, ACCUMULATED into through the reconstruction filter like gbl_render's; a sample whose
+     * feature is NaN is dropped from that film (ImageTile::addSample's rule, GoblinFilm.cpp:62-66) */
+    float* albedo_accum;   /* {sum w*albedo.rgb, sum w}; a miss contributes 0 with its weight */
+    float* normal_accum;   /* {sum w*n.xyz, sum w} */
+    float* depth_accum;    /* {sum w*t*hit, sum w*hit, 0, sum w}: depth = x / y, coverage (alpha) = y / w */
+    gbl_aov_sample* samples_out;     /* one per camera sample of the call, li_out's order */
+} gbl_aov_targets;
+/* Asynchronous on params->stream unless stats != NULL; stats reports paths, extension_rays = paths, kernel_ms and, under
+ * collect_stats, the node / triangle counters.  li_out, russian_roulette and schedule are ignored; the medium, the lights and
+ * max_ray_depth do not enter.  GBL_SAMPLES_STREAM is GBL_ERR_UNSUPPORTED (that stream's image positions depend on the draws Li
+ * makes).  Internal memory is a chunk of samples per pixel at a time, inside gbl_render's per-sample budget.  The films are
+ * ordinary accumulators: gbl_film_allreduce reduces them, gbl_film_resolve normalises the first two. */
+gbl_status gbl_render_aov(gbl_ctx* ctx, const gbl_render_params* params, const gbl_aov_targets* targets, gbl_stats* stats /* or NULL */);
+/* depth_out[W*H] = x / y (IEEE divide) and coverage_out[W*H] (or NULL) = y / w of depth_accum; 0 where the denominator is 0. */
+gbl_status gbl_aov_resolve_depth(gbl_ctx* ctx, const float* depth_accum, float* depth_out, float* coverage_out, void* stream);
+
 /* Device time of recent gbl_render calls, from HIP events recorded on the render stream
  * around the dominant kernel and around the whole call (no host synchronisation happens
  * inside gbl_render for this).  out[0] is the most recent call.  Blocks until those events
