@@ -19,7 +19,7 @@ HOST_DEPS = HOST_SOURCES + [os.path.join(CSRC, "host", "json_lite.h"), os.path.j
 # (a single unit took 3.6 minutes; these take about one on 8 cores, and an edit rebuilds only the units that include
 # what changed -- hipcc's depfiles decide).
 HIP_SOURCES = [os.path.join(CSRC, f) for f in
-               ("gbl_api.hip", "kernels_path.hip", "kernels_quad.hip", "kernels_stream.hip", "kernels_wavefront.hip",
+               ("api_context.hip", "api_render.hip", "api_aov.hip", "api_film.hip", "kernels_path.hip", "kernels_quad.hip", "kernels_stream.hip", "kernels_wavefront.hip",
                 "kernels_whitted.hip", "kernels_aux.hip", "kernels_aov.hip", "scene_prep.cpp")]
 OBJ = os.path.join(LIB, "obj")
 

@@ -1,14 +1,9 @@
-// libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h).
+// libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): the render path.
 //
-// gbl_create   packs the scene on the host (scene_prep.cpp) and uploads it once.
 // gbl_render   launches the persistent render kernel over a sample sub-window and
 //              accumulates into the caller's device film.
-// There is no CPU fallback anywhere in this library: every entry point that
-// computes something needs a HIP device and fails with GBL_ERR_DEVICE otherwise.
-#include <dlfcn.h>
+// plan_samples, launch_splat and close_call are what gbl_render_aov (api_aov.hip) shares with it.
 #include <hip/hip_runtime.h>
-
-#include <chrono>
 
 #include <cmath>
 #include <cstdio>
@@ -17,52 +12,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/goblin_hip.h"
-#include "device_scene.h"
-#include "abi_guard.h"
-#include "gbl_internal.h"
+#include "gbl_host.h"
 #include "kernels/stream.h"     // StreamLayout: the host sizes the stream sampler's scratch
 #include "kernels/trace.h"      // GBL_WF_STACK_LDS
-#include "scene_prep.h"
 
 namespace {
-thread_local std::string g_create_error;
-}
-
-namespace {
-
-template <class T>
-gbl_status upload(gbl_ctx* ctx, const std::vector<T>& v, const T** out) {
-    size_t bytes = std::max<size_t>(1, v.size()) * sizeof(T);
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        ctx->error = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? GBL_ERR_OOM : GBL_ERR_DEVICE;
-    }
-    ctx->allocations.push_back(p);
-    ctx->info.scene_bytes += bytes;
-    if (!v.empty()) HIP_TRY(ctx, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T*>(p);
-    return GBL_OK;
-}
-
-// hipMalloc `capacity` elements and copy the first `count` from the host
-template <class T>
-gbl_status upload_raw(gbl_ctx* ctx, const T* src, size_t count, size_t capacity, const T** out) {
-    size_t bytes = std::max<size_t>(1, capacity) * sizeof(T);
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        ctx->error = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? GBL_ERR_OOM : GBL_ERR_DEVICE;
-    }
-    ctx->allocations.push_back(p);
-    ctx->info.scene_bytes += bytes;
-    if (count) HIP_TRY(ctx, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T*>(p);
-    return GBL_OK;
-}
 
 int round_to_square(int n, int* root) {
     int s = static_cast<int>(std::ceil(std::sqrt(static_cast<float>(n))));
@@ -126,16 +80,10 @@ RenderKnobs read_knobs() {
 }
 
 // What one gbl_render call does, worked out by plan_render (and choose_schedule) before anything is queued
-struct Plan {
-    RenderArgs ra;
-    uint64_t npix = 0;          // pixels of the window
-    uint64_t entries = 0;       // ... times spp: the camera samples of the window, the per-sample buffers' length
+struct Plan : SamplePlan {
     uint64_t call_paths = 0;    // camera samples of this rank's shard (AUTO goes by them)
     uint64_t n_items = 0;       // the megakernel's work items: the shard's tiles x chunks of their samples
-    int total_tiles = 0;
     bool stream_mode = false;   // GBL_SAMPLES_STREAM
-    bool replay = false;        // the kernels read sample records: replay and stream
-    bool want_stats = false;    // collect_stats: instrumented builds
     bool whitted = false;
     size_t lds = 0;             // dynamic LDS of the one-ray-per-lane megakernel ...
     int per_cu = 1;             // ... and the workgroups per CU it leaves room for
@@ -145,54 +93,10 @@ struct Plan {
     int pass_spp = 0;           // ... wavefront: samples per pixel of one pass
 };
 
-// Sets the context's error text and returns the status
-gbl_status fail(gbl_ctx* ctx, gbl_status st, std::string what) {
-    ctx->error = std::move(what);
-    return st;
-}
-
-// Grow a device buffer of the context to at least `bytes`; what it held is not kept
-gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what) {
-    if (bytes <= b.bytes) return GBL_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    const hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        ctx->error = std::string("hipMalloc(") + what + "): " + hipGetErrorString(e);
-        return GBL_ERR_OOM;
-    }
-    b.bytes = bytes;
-    return GBL_OK;
-}
-
-// A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it first
-template <class K>
-gbl_status allow_lds(gbl_ctx* ctx, K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
-    return GBL_OK;
-}
-
-// LDS of the film tile the splat accumulates into, and of a workgroup's traversal stacks
+// LDS of the film tile the splat accumulates into
 size_t tile_lds_bytes(const DevScene& sc) {
     const int tp = GBL_TILE + 2 * sc.film.halo;
     return sizeof(float) * (4 * tp * tp + 256);
-}
-size_t stack_lds_bytes(const DevScene& sc) { return static_cast<size_t>(sc.stack_entries) * GBL_BLOCK * sizeof(uint32_t); }
-
-template <class T>
-gbl_status wf_alloc(gbl_ctx* ctx, T** out, size_t count) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, count * sizeof(T));
-    if (e != hipSuccess) {
-        ctx->error = std::string("hipMalloc(wavefront pool): ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? GBL_ERR_OOM : GBL_ERR_DEVICE;
-    }
-    ctx->allocations.push_back(p);
-    *out = static_cast<T*>(p);
-    return GBL_OK;
 }
 
 gbl_status wf_ensure_pool(gbl_ctx* ctx) {
@@ -201,7 +105,8 @@ gbl_status wf_ensure_pool(gbl_ctx* ctx) {
     WfArgs& w = ctx->wf;
     memset(&w, 0, sizeof(w));
     gbl_status st;
-#define WF_A(field, n) if ((st = wf_alloc(ctx, &w.field, (n))) != GBL_OK) return st
+#define WF_A(field, n) \
+    if ((st = device_alloc(ctx, (n) * sizeof(*w.field), "wavefront pool", reinterpret_cast<void**>(&w.field))) != GBL_OK) return st
     WF_A(ray_o, pool); WF_A(ray_d, pool); WF_A(hit, pool); WF_A(hit_inst, pool);
     WF_A(s_thr, pool); WF_A(s_li, pool); WF_A(s_ld, pool); WF_A(s_f, pool); WF_A(s_id, pool); WF_A(s_vis, pool);
     WF_A(ext_q, pool); WF_A(ext_count, pool / 64);
@@ -218,18 +123,6 @@ gbl_status wf_ensure_pool(gbl_ctx* ctx) {
     }
     ctx->wf_pool = pool;
     return GBL_OK;
-}
-
-// Budget for the per-sample radiance buffer: a quarter of the device's memory (72 GB of the MI355X's 288 GB), so that
-// BASELINE's largest frame (config 3: 1028^2 px x 1024 spp x 16 B = 17.3 GB) is one pass.
-uint64_t li_budget_bytes(gbl_ctx* ctx) {
-    if (ctx->li_budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = 8ull << 30;
-        ctx->li_budget = std::max<uint64_t>(1ull << 30, static_cast<uint64_t>(total_b) / 4);
-        if (const char* e = getenv("GBL_LI_BUDGET_MB")) ctx->li_budget = std::max<uint64_t>(1ull << 20, strtoull(e, nullptr, 10) << 20);
-    }
-    return ctx->li_budget;
 }
 
 // Random numbers one camera sample's transmittance + Lv may draw (GBL_SAMPLES_STREAM sizes a pixel's tail with it): 9 per light
@@ -352,8 +245,7 @@ gbl_status render_wavefront(gbl_ctx* ctx, const gbl_render_params* p, const Plan
         return fail(ctx, GBL_ERR_DEVICE, "wavefront trace grids exceed the stack backing");
     dim3 block(GBL_BLOCK), grid_ext(ext_wgs), grid_shd(shd_wgs), grid_shade(pool / GBL_BLOCK);
     gbl_wf_kernel k_shade = gbl_kernel_wf_shade(replay, want_stats, ext || want_stats);
-    gbl_wf_kernel k_splat = gbl_kernel_wf_splat(replay, want_stats);
-    if (!k_ext || !k_shd || !k_shade || !k_splat) return fail(ctx, GBL_ERR_UNSUPPORTED, "wavefront kernel variant not built");
+    if (!k_ext || !k_shd || !k_shade) return fail(ctx, GBL_ERR_UNSUPPORTED, "wavefront kernel variant not built");
     if ((st = allow_lds(ctx, k_ext, lds_stack)) != GBL_OK || (st = allow_lds(ctx, k_shd, lds_stack)) != GBL_OK) return st;
     for (int k0 = 0; k0 < ra.spp; k0 += pass_spp) {
         wa.pass_k0 = k0;
@@ -395,300 +287,12 @@ gbl_status render_wavefront(gbl_ctx* ctx, const gbl_render_params* p, const Plan
             if (iter > (1u << 20)) return fail(ctx, GBL_ERR_DEVICE, "wavefront loop did not terminate");
         }
         if (overlap && shadow_pending) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->wf_ev_shadow, 0));   // rejoin before the pool is reused
-        hipLaunchKernelGGL(k_splat, dim3(ra.local_tiles), block, tile_lds_bytes(sc), stream, sc, ra, wa);
-        HIP_TRY(ctx, hipGetLastError());
+        if ((st = launch_splat(ctx, ra, wa.li_buf, k0, pass_spp, replay, want_stats, stream)) != GBL_OK) return st;
     }
     HIP_TRY(ctx, hipEventRecord(main_done, stream));
     return GBL_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gbl_abi_version(void) { return GBL_ABI_VERSION; }
-
-const char* gbl_last_error(const gbl_ctx* ctx) { return ctx ? ctx->error.c_str() : g_create_error.c_str(); }
-
-gbl_status gbl_create(const gbl_scene_desc* desc, int device, gbl_ctx** out) {
-    const char* e = getenv("GBL_BVH_BUILD");
-    return gbl_create_ex(desc, device, (e && !strcmp(e, "device")) ? GBL_CREATE_DEVICE_BVH : 0u, out);
-}
-
-static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uint32_t flags, gbl_ctx** out) {
-    const bool device_bvh = (flags & GBL_CREATE_DEVICE_BVH) != 0;
-    if (!desc || !out) {
-        g_create_error = "null argument";
-        return GBL_ERR_INVALID;
-    }
-    *out = nullptr;
-    PackedScene packed;
-    std::string err;
-    auto t_pack0 = std::chrono::steady_clock::now();
-    gbl_status st = pack_scene(desc, &packed, &err, device_bvh);
-    if (st != GBL_OK) {
-        g_create_error = err;
-        return st;
-    }
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || device < 0 || device >= count) {
-        g_create_error = "no HIP device " + std::to_string(device) + " (" +
-                         (e != hipSuccess ? hipGetErrorString(e) : "device count " + std::to_string(count)) +
-                         "); the device integrator has no CPU fallback";
-        return GBL_ERR_DEVICE;
-    }
-    gbl_ctx* ctx = new gbl_ctx();
-    ctx->device = device;
-    memset(&ctx->scene, 0, sizeof(ctx->scene));
-    memset(&ctx->info, 0, sizeof(ctx->info));
-    auto bail = [&](gbl_status s) {
-        g_create_error = ctx->error;
-        gbl_destroy(ctx);
-        return s;
-    };
-    if (hipSetDevice(device) != hipSuccess) {
-        ctx->error = "hipSetDevice failed";
-        return bail(GBL_ERR_DEVICE);
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
-    DevScene& sc = ctx->scene;
-    std::vector<float> ftab(packed.filter_table, packed.filter_table + 256);
-    if (!device_bvh) {
-        if ((st = upload(ctx, packed.nodes, &sc.nodes)) != GBL_OK) return bail(st);
-        if ((st = upload(ctx, packed.tris, &sc.tris)) != GBL_OK) return bail(st);
-    } else {
-        // nodes = [TLAS (from the host) | mesh 0 | mesh 1 | ...], tris = every mesh's triangles in Morton order
-        size_t node_cap = packed.nodes.size(), tri_cap = 0;
-        for (uint32_t m = 0; m < desc->num_meshes; ++m)
-            if (desc->meshes[m].shape == GBL_SHAPE_MESH) {
-                node_cap += desc->meshes[m].tri_count;
-                tri_cap += desc->meshes[m].tri_count;
-            }
-        // device buffers are allocated at their final size; only the TLAS nodes and the raw geometry cross PCIe
-        if ((st = upload_raw(ctx, packed.nodes.data(), packed.nodes.size(), node_cap, &sc.nodes)) != GBL_OK) return bail(st);
-        if ((st = upload_raw(ctx, static_cast<const DevTri*>(nullptr), 0, tri_cap, &sc.tris)) != GBL_OK) return bail(st);
-        const float* d_pos = nullptr;
-        const uint32_t* d_idx = nullptr;
-        const size_t n_pos = 3 * static_cast<size_t>(desc->num_vertices), n_idx = 3 * static_cast<size_t>(desc->num_triangles);
-        if ((st = upload_raw(ctx, desc->positions, n_pos, n_pos, &d_pos)) != GBL_OK) return bail(st);
-        if ((st = upload_raw(ctx, desc->indices, n_idx, n_idx, &d_idx)) != GBL_OK) return bail(st);
-        std::vector<int32_t> mesh_root(desc->num_meshes, 0);
-        int32_t node_base = static_cast<int32_t>(packed.nodes.size());
-        uint32_t tri_base = 0;
-        int max_depth = 0;
-        for (uint32_t m = 0; m < desc->num_meshes; ++m) {
-            const gbl_mesh& gm = desc->meshes[m];
-            if (gm.shape != GBL_SHAPE_MESH) continue;
-            uint32_t used = 0;
-            int depth = 0;
-            st = gbl_build_blas_device(ctx, d_pos + 3 * static_cast<size_t>(gm.vertex_offset), d_idx + 3 * static_cast<size_t>(gm.tri_offset), gm.tri_count,
-                                   &packed.mesh_lo[3 * m], &packed.mesh_hi[3 * m], const_cast<DevNode*>(sc.nodes), node_base,
-                                   const_cast<DevTri*>(sc.tris), tri_base, gm.tri_offset, (gm.has_normal ? 1u : 0u) | (gm.has_uv ? 2u : 0u), &mesh_root[m], &used, &depth);
-            if (st != GBL_OK) return bail(st);
-            node_base += static_cast<int32_t>(used);
-            tri_base += gm.tri_count;
-            max_depth = std::max(max_depth, depth);
-            packed.mesh_stack_need[m] = 3 * depth;
-        }
-        for (size_t i = 0; i < packed.instances.size(); ++i)
-            if (packed.instances[i].shape == 0u) packed.instances[i].root = mesh_root[packed.instances[i].mesh];
-        for (uint32_t m = 0; m < desc->num_meshes; ++m)
-            if (desc->meshes[m].shape == GBL_SHAPE_MESH) packed.mesh_root[m] = mesh_root[m];
-        packed.blas_max_depth = max_depth;
-        packed.blas_nodes = static_cast<uint64_t>(node_base) - packed.nodes.size();
-        {   // device-built trees: the per-level bound of each mesh's BLAS under the exact TLAS sum
-            const std::vector<DevNode> tl(packed.nodes.begin() + packed.tlas_base, packed.nodes.begin() + packed.tlas_base + static_cast<std::ptrdiff_t>(packed.tlas_nodes));
-            packed.stack_entries = scene_stack_entries(tl, packed.tlas_base, packed.tlas_root, packed.instances, packed.mesh_stack_need);
-        }
-        packed.tris.resize(tri_cap);   // for gbl_info only
-    }
-    ctx->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pack0).count();
-    if ((st = upload(ctx, packed.tri_shade, &sc.tri_shade)) != GBL_OK) return bail(st);
-    if (!device_bvh) {
-        if ((st = upload(ctx, packed.tri_bounds_leaf, &sc.tri_bounds)) != GBL_OK) return bail(st);
-    } else {
-        const DevTriBound* by_id = nullptr;
-        if ((st = upload(ctx, packed.tri_bounds, &by_id)) != GBL_OK) return bail(st);
-        if ((st = upload_raw(ctx, static_cast<const DevTriBound*>(nullptr), 0, packed.tris.size(), &sc.tri_bounds)) != GBL_OK) return bail(st);
-        gbl_launch_tri_bounds_gather(sc.tris, by_id, const_cast<DevTriBound*>(sc.tri_bounds), static_cast<uint32_t>(packed.tris.size()));
-        if (hipError_t le = hipGetLastError(); le != hipSuccess) {
-            ctx->error = std::string("triangle bound gather: ") + hipGetErrorString(le);
-            return bail(GBL_ERR_DEVICE);
-        }
-    }
-    if ((st = upload(ctx, packed.tri_order, &sc.tri_order)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.instance_bounds, &sc.instance_bounds)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.positions, &sc.positions)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.normals, &sc.normals)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.uvs, &sc.uvs)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.instances, &sc.instances)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.materials, &sc.materials)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.textures, &sc.textures)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.lights, &sc.lights)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.light_tris, &sc.light_tris)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.light_cdf, &sc.light_cdf)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.light_pick_pdf, &sc.light_pick_pdf)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, ftab, &sc.filter_table)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.images, &sc.images)) != GBL_OK) return bail(st);
-    if ((st = upload_raw(ctx, desc->texels, desc->num_texels, desc->num_texels, &sc.texels)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.ewa_lut, &sc.ewa_lut)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.ibl_dist, &sc.ibl_dist)) != GBL_OK) return bail(st);
-    if ((st = upload(ctx, packed.vol_density, &sc.vol_density)) != GBL_OK) return bail(st);
-    sc.has_ibl = packed.has_ibl;
-    sc.hot_nodes = packed.hot_nodes;
-    ctx->has_images = desc->num_images > 0;
-    sc.tlas_root = packed.tlas_root;
-    sc.num_instances = static_cast<int32_t>(packed.instances.size());
-    sc.num_lights = static_cast<int32_t>(packed.lights.size());
-    for (const DevLight& l : packed.lights) ctx->h_light_slots.push_back(l.wh_n);
-    sc.stack_entries = packed.stack_entries;
-    sc.extended = packed.extended;
-    sc.has_masks = packed.has_masks;
-    sc.has_bssrdf = packed.has_bssrdf;
-    sc.wh_slots = packed.wh_slots;
-    sc.volume = packed.volume;
-    sc.camera = packed.camera;
-    sc.film = packed.film;
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(uint32_t)) != hipSuccess) {
-        ctx->error = "hipMalloc(work counter) failed";
-        return bail(GBL_ERR_OOM);
-    }
-    ctx->allocations.push_back(p);
-    ctx->work_counter = static_cast<uint32_t*>(p);
-    if (hipMalloc(&p, 32 * sizeof(unsigned long long)) != hipSuccess) {
-        ctx->error = "hipMalloc(stats) failed";
-        return bail(GBL_ERR_OOM);
-    }
-    ctx->allocations.push_back(p);
-    ctx->stats = static_cast<unsigned long long*>(p);
-    if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
-        ctx->error = "hipEventCreate failed";
-        return bail(GBL_ERR_DEVICE);
-    }
-    ctx->info.xres = packed.film.xres;
-    ctx->info.yres = packed.film.yres;
-    memcpy(ctx->info.window, packed.film.window, sizeof(ctx->info.window));
-    ctx->info.blas_nodes = packed.blas_nodes;
-    ctx->info.tlas_nodes = packed.tlas_nodes;
-    ctx->info.triangles = packed.tris.size();
-    ctx->info.instances = packed.instances.size();
-    ctx->h_instances.assign(desc->instances, desc->instances + desc->num_instances);
-    ctx->h_meshes.assign(desc->meshes, desc->meshes + desc->num_meshes);
-    ctx->h_materials.assign(desc->materials, desc->materials + desc->num_materials);
-    ctx->mesh_lo = packed.mesh_lo;
-    ctx->mesh_hi = packed.mesh_hi;
-    ctx->mesh_root = packed.mesh_root;
-    ctx->tlas_base = packed.tlas_base;
-    ctx->tlas_capacity = packed.tlas_capacity;
-    ctx->blas_depth = packed.blas_max_depth;
-    ctx->mesh_stack_need = packed.mesh_stack_need;
-    if (getenv("GBL_PROBE"))
-        fprintf(stderr, "probe: traversal stack entries %d (per-level bound %d: TLAS depth %d, BLAS depth %d)\n", packed.stack_entries,
-                3 * (packed.tlas_depth + packed.blas_max_depth) + 2, packed.tlas_depth, packed.blas_max_depth);
-    for (uint32_t i = 0; i < desc->num_lights; ++i)
-        if (desc->lights[i].type == GBL_LIGHT_DIRECTIONAL || desc->lights[i].type == GBL_LIGHT_IBL) ctx->has_directional = true;   // lights sized by the scene bound
-    ctx->info.build_ms = ctx->build_ms;
-    ctx->info.blas_depth = packed.blas_max_depth;
-    ctx->info.tlas_depth = packed.tlas_depth;
-    ctx->info.instanced_triangles = 0;
-    for (uint32_t i = 0; i < desc->num_instances; ++i) ctx->info.instanced_triangles += desc->meshes[desc->instances[i].mesh].tri_count;
-    *out = ctx;
-    return GBL_OK;
-}
-gbl_status gbl_create_ex(const gbl_scene_desc* desc, int device, uint32_t flags, gbl_ctx** out) {
-    return gbl_guard([&] { return gbl_create_ex_impl(desc, device, flags, out); }, [&](const std::string& what) { g_create_error = what; });
-}
-
-static gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
-    if (!ctx) return GBL_ERR_INVALID;
-    if (!to_world || static_cast<uint64_t>(first) + count > ctx->h_instances.size()) {
-        ctx->error = "gbl_update_instances: instance range out of bounds";
-        return GBL_ERR_INVALID;
-    }
-    if (ctx->has_directional) {
-        ctx->error = "gbl_update_instances: a directional or image based light's power (and the image based light's sampling sphere) "
-                     "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead";
-        return GBL_ERR_UNSUPPORTED;
-    }
-    for (uint32_t i = 0; i < count; ++i)
-        if (ctx->h_instances[first + i].area_light >= 0) {
-            ctx->error = "gbl_update_instances: instance " + std::to_string(first + i) + " carries an area light, whose own transform would "
-                         "have to move with it; re-create the context instead";
-            return GBL_ERR_UNSUPPORTED;
-        }
-    std::vector<gbl_instance> edited = ctx->h_instances;
-    for (uint32_t i = 0; i < count; ++i) edited[first + i].to_world = to_world[i];
-    std::vector<DevInstance> inst;
-    std::vector<DevNode> tlas;
-    int32_t root = 0;
-    int depth = 0;
-    float lo[3], hi[3];
-    std::string err;
-    std::vector<DevInstanceBound> bounds;
-    gbl_status st = build_tlas(edited.data(), static_cast<uint32_t>(edited.size()), ctx->h_meshes.data(), ctx->h_materials.data(), ctx->mesh_lo.data(),
-                               ctx->mesh_hi.data(), ctx->mesh_root.data(), ctx->tlas_base, &inst, &tlas, &root, &depth, lo, hi, &err, &bounds);
-    if (st != GBL_OK) {
-        ctx->error = err;
-        return st;
-    }
-    if (tlas.size() > ctx->tlas_capacity) {
-        ctx->error = "gbl_update_instances: rebuilt TLAS does not fit its reserved nodes";
-        return GBL_ERR_DEVICE;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the old TLAS
-    DevScene& sc = ctx->scene;
-    if (!inst.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstance*>(sc.instances), inst.data(), inst.size() * sizeof(DevInstance), hipMemcpyHostToDevice));
-    if (!bounds.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstanceBound*>(sc.instance_bounds), bounds.data(), bounds.size() * sizeof(DevInstanceBound), hipMemcpyHostToDevice));
-    if (!tlas.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevNode*>(sc.nodes) + ctx->tlas_base, tlas.data(), tlas.size() * sizeof(DevNode), hipMemcpyHostToDevice));
-    sc.tlas_root = root;
-    sc.stack_entries = scene_stack_entries(tlas, ctx->tlas_base, root, inst, ctx->mesh_stack_need);   // (the wavefront stack backing is re-checked at render time)
-    ctx->info.tlas_depth = depth;
-    ctx->info.tlas_nodes = tlas.size();
-    ctx->h_instances.swap(edited);
-    ctx->auto_rays_per_path.clear();   // the edited scene's paths may be longer or shorter: AUTO measures again
-    return GBL_OK;
-}
-gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
-    return gbl_guard([&] { return gbl_update_instances_impl(ctx, first, count, to_world); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
-}
-
-void gbl_destroy(gbl_ctx* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    for (void* p : ctx->allocations) (void)hipFree(p);
-    for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->aov, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
-                       &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter})
-        if (b->p) (void)hipFree(b->p);
-    if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
-    if (ctx->wf_ev_shade) (void)hipEventDestroy(ctx->wf_ev_shade);
-    if (ctx->wf_ev_shadow) (void)hipEventDestroy(ctx->wf_ev_shadow);
-    if (ctx->wf_aux) (void)hipStreamDestroy(ctx->wf_aux);
-    if (ctx->wf_host_flags) (void)hipHostFree(ctx->wf_host_flags);
-    for (int i = 0; i < gbl_ctx::kTimingRing; ++i)
-        for (int k = 0; k < 3; ++k)
-            if (ctx->t_ev[i][k]) (void)hipEventDestroy(ctx->t_ev[i][k]);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->rccl) dlclose(ctx->rccl);
-    delete ctx;
-}
-
-gbl_status gbl_get_info(const gbl_ctx* ctx, gbl_info* out) {
-    if (!ctx || !out) return GBL_ERR_INVALID;
-    *out = ctx->info;
-    return GBL_OK;
-}
-
-}   // extern "C"
-
-namespace {
 // The first n values of libc rand() in a process that never called srand() -- what the reference seeds its per-tile
 // generators with (RNGImp::RNGImp, GoblinUtils.cpp:19-20).  glibc's default is the TYPE_3 additive feedback generator
 // over 31 words, r[i] = r[i-3] + r[i-31], seeded with 1 through the Park-Miller step and run 310 times before the
@@ -746,6 +350,98 @@ void sample_layout(const DevScene& sc, const gbl_render_params* p, RenderArgs& r
     }
 }
 
+}   // namespace
+
+// ---------------------------------------------------------------------------
+// What gbl_render shares with gbl_render_aov (gbl_host.h)
+// ---------------------------------------------------------------------------
+// Budget for the per-sample radiance buffer: a quarter of the device's memory (72 GB of the MI355X's 288 GB), so that
+// BASELINE's largest frame (config 3: 1028^2 px x 1024 spp x 16 B = 17.3 GB) is one pass.  GBL_LI_BUDGET_MB overrides it.
+uint64_t li_budget_bytes(gbl_ctx* ctx) {
+    if (ctx->li_budget == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = 8ull << 30;
+        ctx->li_budget = std::max<uint64_t>(1ull << 30, static_cast<uint64_t>(total_b) / 4);
+        if (const char* e = getenv("GBL_LI_BUDGET_MB")) ctx->li_budget = std::max<uint64_t>(1ull << 20, strtoull(e, nullptr, 10) << 20);
+    }
+    return ctx->li_budget;
+}
+
+gbl_status plan_samples(gbl_ctx* ctx, const gbl_render_params* p, bool check_schedule, SamplePlan* pl) {
+    const DevScene& sc = ctx->scene;
+    RenderArgs& ra = pl->ra;
+    memset(&ra, 0, sizeof(ra));
+    if (p->integrator != GBL_INTEGRATOR_PATH && p->integrator != GBL_INTEGRATOR_AO && p->integrator != GBL_INTEGRATOR_WHITTED)
+        return fail(ctx, GBL_ERR_INVALID, "unknown integrator");
+    if (p->sample_per_pixel < 1 || p->max_ray_depth < 1) return fail(ctx, GBL_ERR_INVALID, "sample_per_pixel and max_ray_depth must be >= 1");
+    if (check_schedule && p->schedule > GBL_SCHEDULE_WAVEFRONT) return fail(ctx, GBL_ERR_INVALID, "unknown schedule " + std::to_string(p->schedule));
+    sample_layout(sc, p, ra);
+    const int32_t* full = sc.film.window;
+    const bool whole = p->window[0] == 0 && p->window[1] == 0 && p->window[2] == 0 && p->window[3] == 0;
+    for (int i = 0; i < 4; ++i) ra.window[i] = whole ? full[i] : p->window[i];
+    if (ra.window[0] < full[0] || ra.window[1] > full[1] || ra.window[2] < full[2] || ra.window[3] > full[3] ||
+        ra.window[0] > ra.window[1] || ra.window[2] > ra.window[3])
+        return fail(ctx, GBL_ERR_INVALID, "render window lies outside the film's sample window");
+    if (p->sample_mode == GBL_SAMPLES_REPLAY && !p->replay_samples) return fail(ctx, GBL_ERR_INVALID, "replay mode needs replay_samples");
+    if (p->sample_mode != GBL_SAMPLES_REPLAY && p->sample_mode != GBL_SAMPLES_NATIVE && p->sample_mode != GBL_SAMPLES_STREAM)
+        return fail(ctx, GBL_ERR_INVALID, "unknown sample_mode");
+    pl->npix = static_cast<uint64_t>(ra.window[1] - ra.window[0]) * (ra.window[3] - ra.window[2]);
+    if (pl->npix * ra.spp >= (1ull << 32)) return fail(ctx, GBL_ERR_INVALID, "more than 2^32 camera samples in one call: split the window");
+    pl->entries = pl->npix * ra.spp;
+    ra.tiles_x = (ra.window[1] - ra.window[0] + GBL_TILE - 1) / GBL_TILE;
+    ra.tiles_y = (ra.window[3] - ra.window[2] + GBL_TILE - 1) / GBL_TILE;
+    ra.shard_count = std::max(1, p->tile_shard_count);
+    ra.shard_index = p->tile_shard_count > 1 ? p->tile_shard_index : 0;
+    if (ra.shard_index < 0 || ra.shard_index >= ra.shard_count) return fail(ctx, GBL_ERR_INVALID, "tile_shard_index out of range");
+    pl->total_tiles = ra.tiles_x * ra.tiles_y;
+    ra.local_tiles = pl->total_tiles > ra.shard_index ? (pl->total_tiles - ra.shard_index + ra.shard_count - 1) / ra.shard_count : 0;
+    ra.seed_key = host_mix(static_cast<uint32_t>(p->seed), static_cast<uint32_t>(p->seed >> 32));
+    ra.replay = p->replay_samples;
+    ra.work_counter = ctx->work_counter;
+    ra.stats = ctx->stats;
+    pl->replay = p->sample_mode != GBL_SAMPLES_NATIVE;
+    pl->want_stats = p->collect_stats != 0;
+    return GBL_OK;
+}
+
+gbl_status launch_splat(gbl_ctx* ctx, const RenderArgs& ra, float4* li, int pass_k0, int pass_spp, bool replay, bool stats, hipStream_t stream) {
+    WfArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.li_buf = li;
+    wa.pass_k0 = pass_k0;
+    wa.pass_spp = pass_spp;
+    gbl_wf_kernel k_splat = gbl_kernel_wf_splat(replay, stats);
+    if (!k_splat) return fail(ctx, GBL_ERR_UNSUPPORTED, "splat kernel variant not built");
+    hipLaunchKernelGGL(k_splat, dim3(ra.local_tiles), dim3(GBL_BLOCK), tile_lds_bytes(ctx->scene), stream, ctx->scene, ra, wa);
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+
+// Pixels of the window in the tiles of the call's shard
+static uint64_t shard_pixels(const RenderArgs& ra, int total_tiles) {
+    uint64_t n = 0;
+    for (int t = ra.shard_index; t < total_tiles; t += ra.shard_count) {
+        const int tx = t % ra.tiles_x, ty = t / ra.tiles_x;
+        n += static_cast<uint64_t>(std::min(GBL_TILE, ra.window[1] - (ra.window[0] + GBL_TILE * tx))) *
+             std::min(GBL_TILE, ra.window[3] - (ra.window[2] + GBL_TILE * ty));
+    }
+    return n;
+}
+
+gbl_status close_call(gbl_ctx* ctx, const SamplePlan& pl, hipStream_t stream, gbl_stats* stats, unsigned long long* counters) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    memset(stats, 0, sizeof(*stats));
+    stats->kernel_ms = ms;
+    stats->paths = shard_pixels(pl.ra, pl.total_tiles) * pl.ra.spp;
+    if (pl.want_stats && counters) HIP_TRY(ctx, hipMemcpy(counters, ctx->stats, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return GBL_OK;
+}
+
+namespace {
+
 // GBL_SAMPLES_STREAM: the checks of plan_render that concern the stream sampler, its layout, and the LDS it adds
 gbl_status plan_stream(gbl_ctx* ctx, const gbl_render_params* p, Plan* pl, size_t& lds) {
     const DevScene& sc = ctx->scene;
@@ -784,40 +480,15 @@ gbl_status plan_stream(gbl_ctx* ctx, const gbl_render_params* p, Plan* pl, size_
     return GBL_OK;
 }
 
-// Checks the call's arguments and works out everything about it that needs no device work: the sample layout, the tiling and
-// work items, the stream sampler's layout, the megakernel's LDS and whether it keeps the per-sample radiance, and every budget.
-// The checks keep the order in which the render path used to meet them, so a call failing several gets the first one's
-// status.  Nothing is launched or allocated.  A call with no tiles in its shard leaves here with pl->n_items == 0.
+// Checks the call's arguments and works out everything about it that needs no device work: its camera samples (plan_samples),
+// the work items, the stream sampler's layout, the megakernel's LDS and whether it keeps the per-sample radiance, and every
+// budget.  The checks keep the order in which the render path used to meet them, so a call failing several gets the first
+// one's status.  Nothing is launched or allocated.  A call with no tiles in its shard leaves here with pl->n_items == 0.
 gbl_status plan_render(gbl_ctx* ctx, const gbl_render_params* p, float* film_accum, Plan* pl) {
     const DevScene& sc = ctx->scene;
     RenderArgs& ra = pl->ra;
-    memset(&ra, 0, sizeof(ra));
-    if (p->integrator != GBL_INTEGRATOR_PATH && p->integrator != GBL_INTEGRATOR_AO && p->integrator != GBL_INTEGRATOR_WHITTED)
-        return fail(ctx, GBL_ERR_INVALID, "unknown integrator");
-    if (p->sample_per_pixel < 1 || p->max_ray_depth < 1) return fail(ctx, GBL_ERR_INVALID, "sample_per_pixel and max_ray_depth must be >= 1");
-    if (p->schedule > GBL_SCHEDULE_WAVEFRONT) return fail(ctx, GBL_ERR_INVALID, "unknown schedule " + std::to_string(p->schedule));
-    sample_layout(sc, p, ra);
-    const int32_t* full = sc.film.window;
-    bool whole = p->window[0] == 0 && p->window[1] == 0 && p->window[2] == 0 && p->window[3] == 0;
-    for (int i = 0; i < 4; ++i) ra.window[i] = whole ? full[i] : p->window[i];
-    if (ra.window[0] < full[0] || ra.window[1] > full[1] || ra.window[2] < full[2] || ra.window[3] > full[3] ||
-        ra.window[0] > ra.window[1] || ra.window[2] > ra.window[3]) {
-        ctx->error = "render window lies outside the film's sample window";
-        return GBL_ERR_INVALID;
-    }
-    if (p->sample_mode == GBL_SAMPLES_REPLAY && !p->replay_samples) return fail(ctx, GBL_ERR_INVALID, "replay mode needs replay_samples");
-    if (p->sample_mode != GBL_SAMPLES_REPLAY && p->sample_mode != GBL_SAMPLES_NATIVE && p->sample_mode != GBL_SAMPLES_STREAM)
-        return fail(ctx, GBL_ERR_INVALID, "unknown sample_mode");
-    pl->npix = static_cast<uint64_t>(ra.window[1] - ra.window[0]) * (ra.window[3] - ra.window[2]);
-    if (pl->npix * ra.spp >= (1ull << 32)) return fail(ctx, GBL_ERR_INVALID, "more than 2^32 paths in one call: split the window");
-    pl->entries = pl->npix * ra.spp;
-    ra.tiles_x = (ra.window[1] - ra.window[0] + GBL_TILE - 1) / GBL_TILE;
-    ra.tiles_y = (ra.window[3] - ra.window[2] + GBL_TILE - 1) / GBL_TILE;
-    ra.shard_count = std::max(1, p->tile_shard_count);
-    ra.shard_index = p->tile_shard_count > 1 ? p->tile_shard_index : 0;
-    if (ra.shard_index < 0 || ra.shard_index >= ra.shard_count) return fail(ctx, GBL_ERR_INVALID, "tile_shard_index out of range");
-    pl->total_tiles = ra.tiles_x * ra.tiles_y;
-    ra.local_tiles = pl->total_tiles > ra.shard_index ? (pl->total_tiles - ra.shard_index + ra.shard_count - 1) / ra.shard_count : 0;
+    gbl_status st = plan_samples(ctx, p, true, pl);
+    if (st != GBL_OK) return st;
     // Work granularity: a work item is one tile x one chunk of its samples.  Start
     // at <= 64 samples per item (4096 paths) and keep halving while the launch
     // would have fewer than ~16 items per resident workgroup (tail effect),
@@ -831,25 +502,16 @@ gbl_status plan_render(gbl_ctx* ctx, const gbl_render_params* p, float* film_acc
     if (pl->stream_mode) chunks = 1;   // a work item is a whole tile, walked pixel by pixel (kernels/stream.h)
     ra.chunks = chunks;
     ra.chunk_spp = ra.spp / chunks;
-    ra.seed_key = host_mix(static_cast<uint32_t>(p->seed), static_cast<uint32_t>(p->seed >> 32));
     ra.russian_roulette = p->russian_roulette;
-    ra.replay = p->replay_samples;
     ra.li_out = p->li_out;
     ra.film = film_accum;
-    ra.work_counter = ctx->work_counter;
-    ra.stats = ctx->stats;
     pl->n_items = static_cast<uint64_t>(ra.local_tiles) * ra.chunks;
     if (pl->n_items == 0) return GBL_OK;
     pl->call_paths = pl->entries / static_cast<uint64_t>(ra.shard_count);
-    pl->replay = p->sample_mode == GBL_SAMPLES_REPLAY || pl->stream_mode;
-    pl->want_stats = p->collect_stats != 0;
     pl->whitted = p->integrator == GBL_INTEGRATOR_WHITTED;
     size_t lds = tile_lds_bytes(sc) + 4 * sizeof(uint32_t) + stack_lds_bytes(sc);
     if (lds > 160 * 1024) return fail(ctx, GBL_ERR_UNSUPPORTED, "scene needs " + std::to_string(lds) + " bytes of LDS per workgroup (BVH too deep)");
-    if (pl->stream_mode) {
-        const gbl_status st = plan_stream(ctx, p, pl, lds);
-        if (st != GBL_OK) return st;
-    }
+    if (pl->stream_mode && (st = plan_stream(ctx, p, pl, lds)) != GBL_OK) return st;
     // (plan_stream turns the stream sampler away from GBL_SCHEDULE_WAVEFRONT)
     if (p->schedule == GBL_SCHEDULE_WAVEFRONT && p->integrator != GBL_INTEGRATOR_PATH)
         return fail(ctx, GBL_ERR_UNSUPPORTED, "the wavefront schedule covers the path tracer only");
@@ -1007,19 +669,6 @@ gbl_status first_hit_passes(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl, 
     return GBL_OK;
 }
 
-// The register-accumulating splat (kernels/wavefront.h wf_splat) of a whole call's per-sample radiance into the film
-gbl_status splat_samples(gbl_ctx* ctx, const Plan& pl, float4* li, hipStream_t stream) {
-    WfArgs wa;
-    memset(&wa, 0, sizeof(wa));
-    wa.li_buf = li;
-    wa.pass_k0 = 0;
-    wa.pass_spp = pl.ra.spp;
-    gbl_wf_kernel k_splat = gbl_kernel_wf_splat(pl.replay, pl.want_stats);
-    hipLaunchKernelGGL(k_splat, dim3(pl.ra.local_tiles), dim3(GBL_BLOCK), tile_lds_bytes(ctx->scene), stream, ctx->scene, pl.ra, wa);
-    HIP_TRY(ctx, hipGetLastError());
-    return GBL_OK;
-}
-
 // WhittedRenderer: one lane per camera sample with the recursion's frames in scratch (kernels/whitted.h), then the shared
 // splat kernel.  Its timing window opens again here, after the medium pass.
 gbl_status render_whitted(gbl_ctx* ctx, Plan& pl, const RenderKnobs& knobs, hipEvent_t* tev, bool timed, hipStream_t stream) {
@@ -1063,7 +712,7 @@ gbl_status render_whitted(gbl_ctx* ctx, Plan& pl, const RenderKnobs& knobs, hipE
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(tev[1], stream));
     // replay records of another quota: the splat only reads their image positions, at the Whitted record stride
-    return splat_samples(ctx, pl, li, stream);
+    return launch_splat(ctx, ra, li, 0, ra.spp, pl.replay, pl.want_stats, stream);
 }
 
 // The primary pass (kernels/packet.h): the camera rays of the call traced as packets, one wave per pixel and 64 of its
@@ -1225,7 +874,7 @@ gbl_status render_megakernel(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl,
         HIP_TRY(ctx, hipMemcpy(h, ctx->stats, sizeof(h), hipMemcpyDeviceToHost));
         print_counters(h, true);
     }
-    return pl.defer ? splat_samples(ctx, pl, reinterpret_cast<float4*>(ra.li_defer), stream) : GBL_OK;
+    return pl.defer ? launch_splat(ctx, ra, reinterpret_cast<float4*>(ra.li_defer), 0, ra.spp, pl.replay, want_stats, stream) : GBL_OK;
 }
 
 // Closes the call: the medium's terms into the caller's per-sample output, the timing events, and gbl_stats.  The Whitted
@@ -1239,28 +888,15 @@ gbl_status finish_render(gbl_ctx* ctx, const Plan& pl, const RenderKnobs& knobs,
     HIP_TRY(ctx, hipEventRecord(tev[2], stream));
     ctx->t_calls += 1;
     if (!stats) return GBL_OK;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.0f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    memset(stats, 0, sizeof(*stats));
-    stats->kernel_ms = ms;
+    unsigned long long h[32];
+    const gbl_status st = close_call(ctx, pl, stream, stats, pl.whitted ? nullptr : h);
+    if (st != GBL_OK) return st;
     stats->schedule = pl.wavefront ? GBL_SCHEDULE_WAVEFRONT : GBL_SCHEDULE_MEGAKERNEL;
     if (pl.whitted) {
         stats->paths = pl.entries;
         return GBL_OK;
     }
-    uint64_t shard_pixels = 0;
-    for (int t = ra.shard_index; t < pl.total_tiles; t += ra.shard_count) {
-        int tx = t % ra.tiles_x, ty = t / ra.tiles_x;
-        int tw = std::min(GBL_TILE, ra.window[1] - (ra.window[0] + GBL_TILE * tx));
-        int th = std::min(GBL_TILE, ra.window[3] - (ra.window[2] + GBL_TILE * ty));
-        shard_pixels += static_cast<uint64_t>(tw) * th;
-    }
-    stats->paths = shard_pixels * ra.spp;
     if (!pl.want_stats) return GBL_OK;
-    unsigned long long h[32];
-    HIP_TRY(ctx, hipMemcpy(h, ctx->stats, sizeof(h), hipMemcpyDeviceToHost));
     if (knobs.probe) print_counters(h, false);
     // (the AO kernel of the stream sampler has no instrumented build, gbl_kernel_ao_stream: its launch leaves the device
     //  counters at zero -- report the path count computed above and no ray counters rather than zeros for both)
@@ -1311,158 +947,6 @@ gbl_status gbl_render_impl(gbl_ctx* ctx, const gbl_render_params* p, float* film
     return finish_render(ctx, pl, knobs, tev, stream, stats);
 }
 
-// ---------------------------------------------------------------------------
-// gbl_render_aov: the first-hit feature pass (kernels/aov.h) and one wf_splat per requested film, a chunk of the samples per
-// pixel at a time.  Its plan is the part of plan_render that describes the camera samples of a call -- window, tiles, shard,
-// sample layout, seed -- and none of the integrators' checks and budgets.
-// ---------------------------------------------------------------------------
-struct AovKnobs {
-    bool packet;     // GBL_AOV_PACKET=0: one ray per lane also where the packet kernel applies (A/B, bit-identity test)
-    int pass_spp;    // GBL_AOV_PASS_SPP: at most this many samples per pixel per chunk (tests: force several chunks); 0: the budget's
-};
-AovKnobs read_aov_knobs() {
-    AovKnobs k;
-    const char* e = getenv("GBL_AOV_PACKET");
-    k.packet = e == nullptr || e[0] != '0';
-    e = getenv("GBL_AOV_PASS_SPP");
-    k.pass_spp = e ? std::max(0, atoi(e)) : 0;
-    return k;
-}
-
-gbl_status plan_aov(gbl_ctx* ctx, const gbl_render_params* p, Plan* pl) {
-    const DevScene& sc = ctx->scene;
-    RenderArgs& ra = pl->ra;
-    memset(&ra, 0, sizeof(ra));
-    if (p->integrator != GBL_INTEGRATOR_PATH && p->integrator != GBL_INTEGRATOR_AO && p->integrator != GBL_INTEGRATOR_WHITTED)
-        return fail(ctx, GBL_ERR_INVALID, "unknown integrator");
-    if (p->sample_per_pixel < 1 || p->max_ray_depth < 1) return fail(ctx, GBL_ERR_INVALID, "sample_per_pixel and max_ray_depth must be >= 1");
-    if (p->sample_mode == GBL_SAMPLES_STREAM)
-        return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_render_aov: the image positions of GBL_SAMPLES_STREAM depend on the draws Li makes");
-    if (p->sample_mode != GBL_SAMPLES_REPLAY && p->sample_mode != GBL_SAMPLES_NATIVE) return fail(ctx, GBL_ERR_INVALID, "unknown sample_mode");
-    if (p->sample_mode == GBL_SAMPLES_REPLAY && !p->replay_samples) return fail(ctx, GBL_ERR_INVALID, "replay mode needs replay_samples");
-    sample_layout(sc, p, ra);   // (the integrator and depth fields only size the replay record)
-    const int32_t* full = sc.film.window;
-    const bool whole = p->window[0] == 0 && p->window[1] == 0 && p->window[2] == 0 && p->window[3] == 0;
-    for (int i = 0; i < 4; ++i) ra.window[i] = whole ? full[i] : p->window[i];
-    if (ra.window[0] < full[0] || ra.window[1] > full[1] || ra.window[2] < full[2] || ra.window[3] > full[3] ||
-        ra.window[0] > ra.window[1] || ra.window[2] > ra.window[3])
-        return fail(ctx, GBL_ERR_INVALID, "render window lies outside the film's sample window");
-    pl->npix = static_cast<uint64_t>(ra.window[1] - ra.window[0]) * (ra.window[3] - ra.window[2]);
-    if (pl->npix * ra.spp >= (1ull << 32)) return fail(ctx, GBL_ERR_INVALID, "more than 2^32 camera samples in one call: split the window");
-    pl->entries = pl->npix * ra.spp;
-    ra.tiles_x = (ra.window[1] - ra.window[0] + GBL_TILE - 1) / GBL_TILE;
-    ra.tiles_y = (ra.window[3] - ra.window[2] + GBL_TILE - 1) / GBL_TILE;
-    ra.shard_count = std::max(1, p->tile_shard_count);
-    ra.shard_index = p->tile_shard_count > 1 ? p->tile_shard_index : 0;
-    if (ra.shard_index < 0 || ra.shard_index >= ra.shard_count) return fail(ctx, GBL_ERR_INVALID, "tile_shard_index out of range");
-    pl->total_tiles = ra.tiles_x * ra.tiles_y;
-    ra.local_tiles = pl->total_tiles > ra.shard_index ? (pl->total_tiles - ra.shard_index + ra.shard_count - 1) / ra.shard_count : 0;
-    ra.chunks = 1;
-    ra.chunk_spp = ra.spp;
-    ra.seed_key = host_mix(static_cast<uint32_t>(p->seed), static_cast<uint32_t>(p->seed >> 32));
-    ra.replay = p->replay_samples;
-    ra.work_counter = ctx->work_counter;
-    ra.stats = ctx->stats;
-    pl->replay = p->sample_mode == GBL_SAMPLES_REPLAY;
-    pl->want_stats = p->collect_stats != 0;
-    if (stack_lds_bytes(sc) > 160 * 1024) return fail(ctx, GBL_ERR_UNSUPPORTED, "scene's BVH is too deep for the LDS traversal stacks");
-    return GBL_OK;
-}
-
-gbl_status gbl_render_aov_impl(gbl_ctx* ctx, const gbl_render_params* p, const gbl_aov_targets* tg, gbl_stats* stats, const AovKnobs& knobs) {
-    if (!ctx) return GBL_ERR_INVALID;
-    if (!p || !tg) return fail(ctx, GBL_ERR_INVALID, "null argument");
-    if (!tg->albedo_accum && !tg->normal_accum && !tg->depth_accum && !tg->samples_out)
-        return fail(ctx, GBL_ERR_INVALID, "gbl_render_aov: every target is NULL");
-    Plan pl;
-    gbl_status st = plan_aov(ctx, p, &pl);
-    if (st != GBL_OK) return st;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (pl.ra.local_tiles == 0 || pl.entries == 0) return GBL_OK;
-    const DevScene& sc = ctx->scene;
-    RenderArgs ra = pl.ra;
-    hipStream_t stream = static_cast<hipStream_t>(p->stream);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (pl.want_stats) HIP_TRY(ctx, hipMemsetAsync(ctx->stats, 0, 32 * sizeof(unsigned long long), stream));
-
-    // a chunk's planes: 16 bytes per sample and requested film, inside the per-sample budget gbl_render keeps to
-    float* const films[3] = {tg->albedo_accum, tg->normal_accum, tg->depth_accum};
-    const int n_films = (films[0] ? 1 : 0) + (films[1] ? 1 : 0) + (films[2] ? 1 : 0);
-    int pass_spp = ra.spp;
-    if (n_films > 0) {
-        const uint64_t per_spp = pl.npix * sizeof(float4) * n_films;
-        pass_spp = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(ra.spp, li_budget_bytes(ctx) / per_spp)));
-    }
-    if (knobs.pass_spp > 0) pass_spp = std::min(pass_spp, knobs.pass_spp);
-    float4* planes[3] = {nullptr, nullptr, nullptr};
-    if (n_films > 0) {
-        const uint64_t plane = pl.npix * static_cast<uint64_t>(pass_spp);
-        if ((st = grow(ctx, ctx->aov, plane * sizeof(float4) * n_films, "feature planes")) != GBL_OK) return st;
-        float4* q = static_cast<float4*>(ctx->aov.p);
-        for (int f = 0; f < 3; ++f)
-            if (films[f]) {
-                planes[f] = q;
-                q += plane;
-            }
-    }
-    // Kernel: packets for the lean scenes under the native sampler (see aov_packet_kernel), one ray per lane otherwise.  The
-    // EXT build wherever gbl_render takes one -- feature scenes, replay, instrumented calls -- and with it the tie rule.
-    const bool ext = sc.extended != 0 || pl.replay || pl.want_stats;
-    const bool packet = !ext && knobs.packet && sc.stack_entries <= 64;   // (kernels/packet.h GBL_PACKET_STACK, as primary_pass)
-    gbl_aov_kernel kernel = packet ? gbl_kernel_aov_packet(p->exact_ties != 0) : gbl_kernel_aov(pl.replay, pl.want_stats, ext, p->exact_ties != 0);
-    const size_t lds = stack_lds_bytes(sc);
-    if ((st = allow_lds(ctx, kernel, lds + (packet ? 4096 : 0))) != GBL_OK) return st;   // (the packet kernel's static 3 KB count against the same limit)
-    gbl_wf_kernel k_splat = gbl_kernel_wf_splat(pl.replay, pl.want_stats);
-    if (stats) HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));
-    for (int k0 = 0; k0 < ra.spp; k0 += pass_spp) {
-        AovArgs aa;
-        aa.albedo = planes[0];
-        aa.normal = planes[1];
-        aa.depth = planes[2];
-        aa.samples = tg->samples_out;
-        aa.pass_k0 = k0;
-        aa.pass_spp = std::min(pass_spp, ra.spp - k0);
-        const uint64_t threads = packet ? static_cast<uint64_t>(ra.local_tiles) * 64 * ((aa.pass_spp + 63) / 64) * 64
-                                        : static_cast<uint64_t>(ra.local_tiles) * 64 * aa.pass_spp;
-        const uint64_t cap = static_cast<uint64_t>(ctx->num_cus) * (packet ? 64 : 8);   // grid-stride (the primary pass's grid: 64 workgroups per CU)
-        const dim3 grid(static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>((threads + GBL_BLOCK - 1) / GBL_BLOCK, cap))));
-        hipLaunchKernelGGL(kernel, grid, dim3(GBL_BLOCK), lds, stream, sc, ra, aa);
-        HIP_TRY(ctx, hipGetLastError());
-        WfArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.pass_k0 = k0;
-        wa.pass_spp = aa.pass_spp;
-        for (int f = 0; f < 3; ++f) {
-            if (!films[f]) continue;
-            ra.film = films[f];
-            wa.li_buf = planes[f];
-            hipLaunchKernelGGL(k_splat, dim3(ra.local_tiles), dim3(GBL_BLOCK), tile_lds_bytes(sc), stream, sc, ra, wa);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    if (!stats) return GBL_OK;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, stream));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0.0f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    stats->kernel_ms = ms;
-    uint64_t shard_pixels = 0;
-    for (int t = ra.shard_index; t < pl.total_tiles; t += ra.shard_count) {
-        const int tx = t % ra.tiles_x, ty = t / ra.tiles_x;
-        shard_pixels += static_cast<uint64_t>(std::min(GBL_TILE, ra.window[1] - (ra.window[0] + GBL_TILE * tx))) *
-                        std::min(GBL_TILE, ra.window[3] - (ra.window[2] + GBL_TILE * ty));
-    }
-    stats->paths = stats->extension_rays = shard_pixels * ra.spp;
-    if (pl.want_stats) {
-        unsigned long long h[32];
-        HIP_TRY(ctx, hipMemcpy(h, ctx->stats, sizeof(h), hipMemcpyDeviceToHost));
-        stats->nodes = h[3];
-        stats->tris = h[4];
-        stats->splats = h[5];
-    }
-    return GBL_OK;
-}
-
 }   // namespace
 
 extern "C" {
@@ -1485,113 +969,6 @@ int gbl_get_timings(gbl_ctx* ctx, int n, gbl_timing* out) {
         out[i].total_ms = b;
     }
     return n;
-}
-
-static gbl_status gbl_film_resolve_impl(gbl_ctx* ctx, const float* film_accum, float* rgb_out, void* stream) {
-    if (!ctx || !film_accum || !rgb_out) return GBL_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int n = ctx->info.xres * ctx->info.yres;
-    gbl_launch_film_resolve(film_accum, rgb_out, n, static_cast<hipStream_t>(stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return GBL_OK;
-}
-gbl_status gbl_film_resolve(gbl_ctx* ctx, const float* film_accum, float* rgb_out, void* stream) {
-    return gbl_guard([&] { return gbl_film_resolve_impl(ctx, film_accum, rgb_out, stream); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
-}
-
-// Film::writeImage's tail (GoblinFilm.cpp:164-192 + Goblin::writeImage, GoblinImageIO.cpp:146-237) in passes on one stream:
-// normalise, bloom, tone map, quantise (kernels/develop.h).  Nothing comes back to the host.
-static gbl_status gbl_film_develop_impl(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* p, float* rgb_out, uint8_t* rgb8_out) {
-    if (!ctx || !film_accum || !p || (!rgb_out && !rgb8_out)) return GBL_ERR_INVALID;
-    if (rgb_out == film_accum) {
-        ctx->error = "gbl_film_develop: rgb_out may not alias film_accum";
-        return GBL_ERR_INVALID;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int width = ctx->info.xres, height = ctx->info.yres, n = width * height;
-    hipStream_t stream = static_cast<hipStream_t>(p->stream);
-    gbl_status st;
-    float* rgb = rgb_out;
-    if (!rgb) {
-        if ((st = grow(ctx, ctx->dev_rgb, static_cast<uint64_t>(n) * 3 * sizeof(float), "developed image")) != GBL_OK) return st;
-        rgb = static_cast<float*>(ctx->dev_rgb.p);
-    }
-    int fw = 0;   // Goblin::bloom's filterWidth; 0 taps: nothing to do (as gbl_host_bloom)
-    if (p->bloom_radius > 0.0f && p->bloom_weight > 0.0f) fw = static_cast<int>(std::ceil(p->bloom_radius * std::max(width, height))) / 2;
-    if (fw > 0) {
-        const int fwx = std::min(fw, width), fwy = std::min(fw, height);
-        if ((st = grow(ctx, ctx->dev_rgb1, static_cast<uint64_t>(n) * 4 * sizeof(float), "normalised image")) != GBL_OK) return st;
-        if (ctx->dev_filter_fw != fw) {
-            ctx->dev_filter_fw = 0;
-            if ((st = grow(ctx, ctx->dev_filter, static_cast<uint64_t>(fwx) * fwy * sizeof(float), "bloom filter")) != GBL_OK) return st;
-            gbl_launch_bloom_filter(static_cast<float*>(ctx->dev_filter.p), fw, fwx, fwy, stream);
-            ctx->dev_filter_fw = fw;
-        }
-        gbl_launch_develop_resolve(film_accum, static_cast<float*>(ctx->dev_rgb1.p), n, stream);
-        gbl_launch_bloom(static_cast<const float*>(ctx->dev_rgb1.p), static_cast<const float*>(ctx->dev_filter.p), rgb, width, height, fw, fwx,
-                         p->bloom_weight, stream);
-    } else {
-        gbl_launch_film_resolve(film_accum, rgb, n, stream);
-    }
-    if (p->tone_mapping) {
-        if ((st = grow(ctx, ctx->dev_logs, (static_cast<uint64_t>(n) + 1) * sizeof(float), "tone map sums")) != GBL_OK) return st;
-        float* logs = static_cast<float*>(ctx->dev_logs.p);
-        gbl_launch_tone_map(rgb, logs, logs + n, n, stream);
-    }
-    if (rgb8_out) gbl_launch_quantize(rgb, rgb8_out, 3 * n, stream);
-    HIP_TRY(ctx, hipGetLastError());
-    return GBL_OK;
-}
-gbl_status gbl_film_develop(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* params, float* rgb_out, uint8_t* rgb8_out) {
-    return gbl_guard([&] { return gbl_film_develop_impl(ctx, film_accum, params, rgb_out, rgb8_out); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
-}
-
-gbl_status gbl_render_aov(gbl_ctx* ctx, const gbl_render_params* params, const gbl_aov_targets* targets, gbl_stats* stats) {
-    return gbl_guard([&] { return gbl_render_aov_impl(ctx, params, targets, stats, read_aov_knobs()); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
-}
-
-static gbl_status gbl_aov_resolve_depth_impl(gbl_ctx* ctx, const float* depth_accum, float* depth_out, float* coverage_out, void* stream) {
-    if (!ctx || !depth_accum || !depth_out) return GBL_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    gbl_launch_aov_resolve_depth(depth_accum, depth_out, coverage_out, ctx->info.xres * ctx->info.yres, static_cast<hipStream_t>(stream));
-    HIP_TRY(ctx, hipGetLastError());
-    return GBL_OK;
-}
-gbl_status gbl_aov_resolve_depth(gbl_ctx* ctx, const float* depth_accum, float* depth_out, float* coverage_out, void* stream) {
-    return gbl_guard([&] { return gbl_aov_resolve_depth_impl(ctx, depth_accum, depth_out, coverage_out, stream); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
-}
-
-// ncclAllReduce(sum, float) over the film, resolved from librccl at first use so
-// single-GPU users never load RCCL.
-static gbl_status gbl_film_allreduce_impl(gbl_ctx* ctx, void* rccl_comm, float* film_accum, void* stream) {
-    if (!ctx || !rccl_comm || !film_accum) return GBL_ERR_INVALID;
-    typedef int (*allreduce_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
-    if (!ctx->rccl_allreduce) {
-        ctx->rccl = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!ctx->rccl) ctx->rccl = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!ctx->rccl) {
-            ctx->error = std::string("cannot load librccl: ") + dlerror();
-            return GBL_ERR_DEVICE;
-        }
-        ctx->rccl_allreduce = dlsym(ctx->rccl, "ncclAllReduce");
-        if (!ctx->rccl_allreduce) {
-            ctx->error = "librccl has no ncclAllReduce";
-            return GBL_ERR_DEVICE;
-        }
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t count = static_cast<size_t>(ctx->info.xres) * ctx->info.yres * 4;
-    const int kNcclFloat32 = 7, kNcclSum = 0;
-    int rc = reinterpret_cast<allreduce_fn>(ctx->rccl_allreduce)(film_accum, film_accum, count, kNcclFloat32, kNcclSum, rccl_comm,
-                                                                 static_cast<hipStream_t>(stream));
-    if (rc != 0) {
-        ctx->error = "ncclAllReduce failed with code " + std::to_string(rc);
-        return GBL_ERR_DEVICE;
-    }
-    return GBL_OK;
-}
-gbl_status gbl_film_allreduce(gbl_ctx* ctx, void* rccl_comm, float* film_accum, void* stream) {
-    return gbl_guard([&] { return gbl_film_allreduce_impl(ctx, rccl_comm, film_accum, stream); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 
 }  // extern "C"

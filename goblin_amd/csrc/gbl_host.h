@@ -1,0 +1,56 @@
+// Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
+// api_film.hip) share.  No kernel header is needed to read it.
+#pragma once
+#include <string>
+
+#include "abi_guard.h"
+#include "gbl_internal.h"
+
+// Sets the context's error text and returns the status (api_context.hip)
+gbl_status fail(gbl_ctx* ctx, gbl_status st, std::string what);
+
+// Device memory that lives as long as the context (gbl_destroy frees ctx->allocations): GBL_ERR_OOM when the device is out of
+// memory, GBL_ERR_DEVICE for any other failure, the error text naming `what` (api_context.hip)
+gbl_status device_alloc(gbl_ctx* ctx, size_t bytes, const char* what, void** out);
+
+// Grow a device buffer of the context to at least `bytes`; what it held is not kept (api_context.hip)
+gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what);
+
+// A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it first
+template <class K>
+gbl_status allow_lds(gbl_ctx* ctx, K kernel, size_t bytes) {
+    if (bytes > 64 * 1024)
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+    return GBL_OK;
+}
+
+// LDS of a workgroup's traversal stacks
+inline size_t stack_lds_bytes(const DevScene& sc) { return static_cast<size_t>(sc.stack_entries) * GBL_BLOCK * sizeof(uint32_t); }
+
+// Budget for the per-sample buffers of a call, read once per context (api_render.hip)
+uint64_t li_budget_bytes(gbl_ctx* ctx);
+
+// Which camera samples a call draws, worked out by plan_samples before anything is queued: what gbl_render and
+// gbl_render_aov have in common
+struct SamplePlan {
+    RenderArgs ra;              // sample layout, window, tiling, shard, seed, replay records and the context's counters; the rest zero
+    uint64_t npix = 0;          // pixels of the window
+    uint64_t entries = 0;       // ... times spp: the camera samples of the window, the per-sample buffers' length
+    int total_tiles = 0;
+    bool replay = false;        // the kernels read sample records: replay and stream
+    bool want_stats = false;    // collect_stats: instrumented builds
+};
+
+// Checks the integrator, sample counts, window, sample mode and shard of a call, in the order gbl_render always met them (a
+// call failing several gets the first one's status), and fills the plan.  gbl_render also checks its schedule field, between
+// the sample counts and the window; gbl_render_aov ignores that field.  A shard that owns no tile leaves with
+// ra.local_tiles == 0.  Nothing is launched or allocated.  (api_render.hip)
+gbl_status plan_samples(gbl_ctx* ctx, const gbl_render_params* p, bool check_schedule, SamplePlan* pl);
+
+// The register-accumulating splat (kernels/wavefront.h wf_splat) of per-sample values into ra.film: samples pass_k0 ..
+// pass_k0 + pass_spp of every pixel of the shard's tiles, `li` holding pass_spp values per pixel of the window.  (api_render.hip)
+gbl_status launch_splat(gbl_ctx* ctx, const RenderArgs& ra, float4* li, int pass_k0, int pass_spp, bool replay, bool stats, hipStream_t stream);
+
+// Closes a call that reports gbl_stats: the time since ev0, the shard's camera samples as `paths`, every other field zero;
+// an instrumented call (want_stats) also copies the 32 device counters into `counters`, unless that is NULL.  (api_render.hip)
+gbl_status close_call(gbl_ctx* ctx, const SamplePlan& pl, hipStream_t stream, gbl_stats* stats, unsigned long long* counters);

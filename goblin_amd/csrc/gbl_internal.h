@@ -1,7 +1,7 @@
 // Internal to libgoblin_hip.so: the context behind the C ABI's opaque handle and the table of device kernels.
 //
 // The kernels live in translation units of their own (kernels_*.hip), compiled side by side; the host side of the ABI
-// (gbl_api.hip) picks an instantiation through the selectors below and launches it by pointer.  A selector returns
+// (api_*.hip, gbl_host.h) picks an instantiation through the selectors below and launches it by pointer.  A selector returns
 // nullptr for a combination that is not built.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@
 #include "kernels/wf_args.h"
 #include "kernels/aov_args.h"
 
-// A device buffer of the context, grown on demand (gbl_api.hip grow()) and freed by gbl_destroy
+// A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
     void* p = nullptr;
     uint64_t bytes = 0;

@@ -1,5 +1,5 @@
 // libgoblin_hip.so, kernel unit: the persistent megakernel and the AO kernel, one ray per lane, under the native and
-// replay samplers (kernels/render_kernels.h).  gbl_api.hip launches them through the selectors of gbl_internal.h.
+// replay samplers (kernels/render_kernels.h).  api_render.hip launches them through the selectors of gbl_internal.h.
 #include "gbl_internal.h"
 #include "kernels/render_kernels.h"
 

@@ -5,7 +5,7 @@
 #include "kernels/packet.h"
 
 // (the lean kernels of the native sampler only: the EXT builds are slower under the quad queries, the replay / instrumented builds
-//  run one ray per lane -- gbl_api.hip.  exact_ties: the reference's tie rule and reachability test kept, trace.h TIES)
+//  run one ray per lane -- api_render.hip.  exact_ties: the reference's tie rule and reachability test kept, trace.h TIES)
 gbl_render_kernel gbl_kernel_path_quad(bool exact_ties) {
     return exact_ties ? path_trace_kernel<GBL_SRC_NATIVE, false, false, true, true> : path_trace_kernel<GBL_SRC_NATIVE, false, false, true>;
 }

@@ -180,7 +180,7 @@ int balanced_height(size_t n, int leaf) {
 // Most entries a ray can have on its traversal stack while inside the subtree of `ref` (kernels/trace.h trav_interior: a node
 // whose k children are all hit leaves k - 1 of them on the stack while the first is visited, and any child can be the first).
 // The 3-per-level bound assumes four children at every level of the deepest path; SAH trees of real meshes need about two
-// thirds of it, and the megakernel's LDS stacks are sized by this number (gbl_api.hip: three workgroups per CU or two).
+// thirds of it, and the megakernel's LDS stacks are sized by this number (api_render.hip: three workgroups per CU or two).
 // GBL_STACK_LEVEL_BOUND=1 (a test aid): count three siblings at every node, i.e. the per-level bound the stacks had before.
 static bool stack_level_bound() {
     static const bool on = [] { const char* e = getenv("GBL_STACK_LEVEL_BOUND"); return e != nullptr && e[0] != '\0' && e[0] != '0'; }();
@@ -1288,7 +1288,7 @@ gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* er
         store3x4(t.inv, v.inv);
         if (v.hetero != 0u) {
             // a march is at most (the region's longest world-space diagonal) / step_size points long: bounded at the 10^6 the
-            // stream sampler's draw budget assumes (gbl_api.hip medium_draws_per_sample) -- a step of 1e-12 is a hang, not a render
+            // stream sampler's draw budget assumes (api_render.hip medium_draws_per_sample) -- a step of 1e-12 is a hang, not a render
             double diag = 0.0;
             for (int sgn = 0; sgn < 4; ++sgn) {
                 const double e[3] = {double(v.hi[0] - v.lo[0]), (sgn & 1 ? -1.0 : 1.0) * double(v.hi[1] - v.lo[1]), (sgn & 2 ? -1.0 : 1.0) * double(v.hi[2] - v.lo[2])};

@@ -187,7 +187,7 @@ def test_device_tree_shape_of_the_bundled_meshes(torch, scene_name, extra):
 
 
 def test_deep_tree_renders_past_the_64_entry_stack(torch, scene_dir, monkeypatch):
-    """The deep spiral's device-built tree needs more than 64 traversal stack entries: no primary pass (gbl_api.hip), per-lane
+    """The deep spiral's device-built tree needs more than 64 traversal stack entries: no primary pass (api_render.hip), per-lane
     stacks beyond GBL_PACKET_STACK, more than 64 KB of LDS per megakernel workgroup and the wavefront stacks' spill -- and still
     inside the 160 KB refusal.  Radiance equals the oracle under both schedules and with the wavefront's launches serialised."""
     from goblin_amd.renderer import HipPathTracer
