@@ -1,9 +1,10 @@
 // libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): what happens to a film after the render calls --
-// gbl_film_resolve, gbl_film_develop and the RCCL reduce of gbl_film_allreduce.
+// gbl_film_resolve, gbl_film_develop, gbl_film_variance, gbl_film_denoise and the RCCL reduce of gbl_film_allreduce.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <string>
 
 #include "gbl_host.h"
@@ -67,6 +68,95 @@ static gbl_status gbl_film_develop_impl(gbl_ctx* ctx, const float* film_accum, c
 }
 gbl_status gbl_film_develop(gbl_ctx* ctx, const float* film_accum, const gbl_develop_params* params, float* rgb_out, uint8_t* rgb8_out) {
     return gbl_guard([&] { return gbl_film_develop_impl(ctx, film_accum, params, rgb_out, rgb8_out); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+// Variance of the pixel mean from a call's per-sample radiance (kernels/denoise.h film_variance_kernel)
+static gbl_status gbl_film_variance_impl(gbl_ctx* ctx, const float* li, const int32_t* window, int32_t sample_per_pixel, float* variance_out, void* stream) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!li || !variance_out) return fail(ctx, GBL_ERR_INVALID, "gbl_film_variance: li and variance_out may not be NULL");
+    if (sample_per_pixel < 2) return fail(ctx, GBL_ERR_INVALID, "gbl_film_variance: sample_per_pixel must be >= 2, a variance needs two samples");
+    const int root = static_cast<int>(std::ceil(std::sqrt(static_cast<float>(sample_per_pixel))));   // roundToSquare, as gbl_render
+    const int32_t* full = ctx->info.window;
+    const bool whole = !window || (window[0] == 0 && window[1] == 0 && window[2] == 0 && window[3] == 0);
+    int32_t w[4];
+    for (int i = 0; i < 4; ++i) w[i] = whole ? full[i] : window[i];
+    if (w[0] < full[0] || w[1] > full[1] || w[2] < full[2] || w[3] > full[3] || w[0] > w[1] || w[2] > w[3])
+        return fail(ctx, GBL_ERR_INVALID, "gbl_film_variance: window lies outside the film's sample window");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gbl_launch_film_variance(li, variance_out, w, root * root, ctx->info.xres, ctx->info.yres, static_cast<hipStream_t>(stream));
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+gbl_status gbl_film_variance(gbl_ctx* ctx, const float* li, const int32_t window[4], int32_t sample_per_pixel, float* variance_out, void* stream) {
+    return gbl_guard([&] { return gbl_film_variance_impl(ctx, li, window, sample_per_pixel, variance_out, stream); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+// The a-trous filter (kernels/denoise.h): prepare, one level kernel per iteration between two buffers, finish.
+// Which level kernel serves a stride: the one that stages tile and halo in LDS, or the one that taps global memory.  Measured
+// per stride at 512^2 and 1024^2: staging wins at strides 1 and 2 (-16 ... -35 % of the level), loses from stride 4
+// on, where the halo is most of what is staged, and does not fit a workgroup's LDS from stride 16 on.  GBL_DENOISE_LDS=0 / 1,
+// read per call, forces one of them wherever the staged tile fits (A/B, tests).
+static bool denoise_level_in_lds(int stride) {
+    if (gbl_denoise_lds_bytes(stride) == 0) return false;
+    if (const char* e = getenv("GBL_DENOISE_LDS")) return e[0] != '0';
+    return stride <= 2;
+}
+static bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+static gbl_status gbl_film_denoise_impl(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* albedo_accum, const float* normal_accum,
+                                        const float* depth_accum, const gbl_denoise_params* p, float* film_out) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!film_accum) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: film_accum is NULL");
+    if (!p) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: params is NULL");
+    if (!film_out) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: film_out is NULL");
+    if (p->iterations < 1 || p->iterations > 8) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: iterations must be 1..8, got " + std::to_string(p->iterations));
+    const auto bad = [](float s) { return !(s > 0.0f) || !std::isfinite(s); };
+    if (bad(p->sigma_luminance)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: sigma_luminance must be finite and > 0");
+    if (normal_accum && bad(p->sigma_normal)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: sigma_normal must be finite and > 0");
+    if (albedo_accum && bad(p->sigma_albedo)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: sigma_albedo must be finite and > 0");
+    if (depth_accum && bad(p->sigma_depth)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: sigma_depth must be finite and > 0");
+    if (p->demodulate && !albedo_accum) return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: demodulate needs albedo_accum");
+    const int width = ctx->info.xres, height = ctx->info.yres, n = width * height;
+    const uint64_t film_bytes = static_cast<uint64_t>(n) * 4 * sizeof(float);
+    if (overlaps(film_out, film_bytes, film_accum, film_bytes) || overlaps(film_out, film_bytes, variance, film_bytes / 4) ||
+        overlaps(film_out, film_bytes, albedo_accum, film_bytes) || overlaps(film_out, film_bytes, normal_accum, film_bytes) ||
+        overlaps(film_out, film_bytes, depth_accum, film_bytes))
+        return fail(ctx, GBL_ERR_INVALID, "gbl_film_denoise: film_out may not alias an input");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    gbl_status st;
+    if ((st = grow(ctx, ctx->denoise, 4 * film_bytes, "denoiser planes")) != GBL_OK) return st;
+    float4* cv[2] = {static_cast<float4*>(ctx->denoise.p), static_cast<float4*>(ctx->denoise.p) + n};
+    float4* const nz = cv[1] + n;
+    float4* const af = nz + n;
+    const uint32_t demodulate = p->demodulate ? 1u : 0u;
+    gbl_launch_denoise_prepare(film_accum, variance, albedo_accum, normal_accum, depth_accum, cv[0], nz, af, n, demodulate, stream);
+    HIP_TRY(ctx, hipGetLastError());
+    DenoiseArgs a;
+    a.W = width;
+    a.H = height;
+    a.sigma_l = p->sigma_luminance;
+    a.inv_sn2 = normal_accum ? 1.0f / (p->sigma_normal * p->sigma_normal) : 0.0f;
+    a.inv_sa2 = albedo_accum ? 1.0f / (p->sigma_albedo * p->sigma_albedo) : 0.0f;
+    a.has_var = variance ? 1u : 0u;
+    a.demodulate = demodulate;
+    int cur = 0;
+    for (int level = 0; level < p->iterations; ++level) {
+        a.stride = 1 << level;
+        a.sz = depth_accum ? p->sigma_depth * static_cast<float>(a.stride) : 0.0f;
+        HIP_TRY(ctx, gbl_launch_denoise_level(denoise_level_in_lds(a.stride), cv[cur], nz, af, cv[cur ^ 1], a, stream, &ctx->denoise_lds_allowed));
+        cur ^= 1;
+    }
+    gbl_launch_denoise_finish(cv[cur], af, film_out, n, demodulate, stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+gbl_status gbl_film_denoise(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* albedo_accum, const float* normal_accum,
+                            const float* depth_accum, const gbl_denoise_params* params, float* film_out) {
+    return gbl_guard([&] { return gbl_film_denoise_impl(ctx, film_accum, variance, albedo_accum, normal_accum, depth_accum, params, film_out); },
+                     [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 
 // ncclAllReduce(sum, float) over the film, resolved from librccl at first use so

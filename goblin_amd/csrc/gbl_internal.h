@@ -14,6 +14,7 @@
 #include "device_scene.h"
 #include "kernels/wf_args.h"
 #include "kernels/aov_args.h"
+#include "kernels/denoise_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -57,6 +58,8 @@ struct gbl_ctx {
     gbl_buf dev_logs;         // the tone map's logf(1e4 + luminance) per pixel, then 1 / Ywa^2 in one float after them
     gbl_buf dev_filter;       // the bloom's filter table ...
     int dev_filter_fw = 0;    // ... and the filter width it was built for (0: none yet)
+    gbl_buf denoise;          // gbl_film_denoise's four float4 planes (kernels/denoise.h): cv ping, cv pong, nz, af
+    bool denoise_lds_allowed = false;   // ... its staging level kernel may be launched with more than 64 KB of LDS on this device
     std::map<int, float> auto_rays_per_path;   // GBL_SCHEDULE_AUTO's pilot: rays per camera path by 2 * max_ray_depth + russian_roulette (gbl_render)
     double build_ms = 0.0;    // pack_scene + BVH construction + node / triangle upload
     // what gbl_update_instances needs to rebuild the TLAS
@@ -131,6 +134,14 @@ void gbl_launch_quantize(const float* rgb, uint8_t* rgb8, int n, hipStream_t str
 gbl_aov_kernel gbl_kernel_aov(bool replay, bool stats, bool ext, bool exact_ties);
 gbl_aov_kernel gbl_kernel_aov_packet(bool exact_ties);
 void gbl_launch_aov_resolve_depth(const float* accum, float* depth, float* coverage, int n, hipStream_t stream);
+// kernels_denoise.hip: gbl_film_variance and the passes of gbl_film_denoise (kernels/denoise.h)
+void gbl_launch_film_variance(const float* li, float* variance, const int32_t window[4], int spp, int width, int height, hipStream_t stream);
+void gbl_launch_denoise_prepare(const float* film, const float* variance, const float* albedo, const float* normal, const float* depth, float4* cv,
+                                float4* nz, float4* af, int n, uint32_t demodulate, hipStream_t stream);
+size_t gbl_denoise_lds_bytes(int stride);   // of the staging level kernel; 0 where a workgroup cannot have that much
+hipError_t gbl_launch_denoise_level(bool lds, const float4* cv_in, const float4* nz, const float4* af, float4* cv_out, const DenoiseArgs& a, hipStream_t stream,
+                                    bool* lds_allowed);
+void gbl_launch_denoise_finish(const float4* cv, const float4* af, float* film_out, int n, uint32_t demodulate, hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

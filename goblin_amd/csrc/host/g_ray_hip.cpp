@@ -1,4 +1,9 @@
-// g_ray_hip <scene.json> [--device N] [--seed S] [--sampler native|stream] [--out file.{exr,ppm,pfm}] [--aov]
+// g_ray_hip <scene.json> [--device N] [--seed S] [--sampler native|stream] [--out file.{exr,ppm,pfm}] [--aov] [--denoise[=N]]
+//
+// --denoise[=N] also writes <output stem>.denoised.<ext>: the film filtered by gbl_film_denoise at N levels (default 5), guided
+// by the feature films of gbl_render_aov and, where the frame's per-sample radiance (16 bytes per camera sample) fits the
+// library's per-sample budget, by gbl_film_variance of it; otherwise without a variance plane, which it says on stderr.  The
+// denoised film goes through the same develop and write path as the image; the image itself does not change.  Native sampler only.
 //
 // --aov also writes the first-hit feature films (gbl_render_aov) of the same camera samples beside the image:
 // <output stem>.albedo.pfm, .normal.pfm (both normalised) and .depth.pfm (r = depth, g = coverage, b = 0).  Portable float
@@ -27,16 +32,26 @@
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "Usage: g_ray_hip scene_file.json [--device N] [--seed S] [--sampler native|stream] [--out image.{exr,ppm,pfm}] [--aov]\n");
+        fprintf(stderr, "Usage: g_ray_hip scene_file.json [--device N] [--seed S] [--sampler native|stream] [--out image.{exr,ppm,pfm}] [--aov] [--denoise[=N]]\n");
         return 0;
     }
     std::string scene_path = argv[1], out_path;
     int device = 0;
     unsigned long long seed = 0;
     bool stream_sampler = false, aov = false;
+    int denoise = 0;   // levels; 0: off
     for (int i = 2; i < argc; i += 2) {
-        if (!strcmp(argv[i], "--aov")) {   // (the one switch without a value)
+        if (!strcmp(argv[i], "--aov")) {   // (the switches without a separate value)
             aov = true;
+            i -= 1;
+            continue;
+        }
+        if (!strncmp(argv[i], "--denoise", 9) && (argv[i][9] == 0 || argv[i][9] == '=')) {
+            denoise = argv[i][9] ? atoi(argv[i] + 10) : 5;
+            if (denoise < 1 || denoise > 8) {
+                fprintf(stderr, "--denoise takes 1..8 levels\n");
+                return 1;
+            }
             i -= 1;
             continue;
         }
@@ -48,6 +63,10 @@ int main(int argc, char** argv) {
     }
     if (aov && stream_sampler) {   // (gbl_render_aov refuses GBL_SAMPLES_STREAM: say so before rendering anything)
         fprintf(stderr, "--aov needs the native sampler\n");
+        return 1;
+    }
+    if (denoise && stream_sampler) {
+        fprintf(stderr, "--denoise needs the native sampler\n");
         return 1;
     }
     gbl_host_scene* hs = nullptr;
@@ -81,6 +100,27 @@ int main(int argc, char** argv) {
     p.bssrdf_sample_num = desc->setting.bssrdf_sample_num;
     p.sample_mode = GBL_SAMPLES_NATIVE;
     p.seed = seed;
+    // --denoise: keep the per-sample radiance of the one render below where it fits the budget gbl_render itself keeps its
+    // per-sample buffer inside.  The rule restated here is li_budget_bytes() of api_render.hip -- a quarter of the device's memory,
+    // at least 1 GiB, GBL_LI_BUDGET_MB instead when set -- and has to follow it: inside that budget plan_render defers the splat
+    // (`defer`) with or without li_out and choose_schedule does not split the call into passes, so the call runs under the
+    // schedule it would run under without li_out (tests/test_gpu_denoise.py holds the two calls to one schedule and one film).
+    float* li = nullptr;
+    if (denoise) {
+        const unsigned long long spp = static_cast<unsigned long long>(gbl_host_round_to_square(p.sample_per_pixel));
+        const unsigned long long li_bytes = static_cast<unsigned long long>(info.window[1] - info.window[0]) * (info.window[3] - info.window[2]) * spp * 16ull;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = 8ull << 30;
+        unsigned long long budget = std::max<unsigned long long>(1ull << 30, total_b / 4);
+        if (const char* e = getenv("GBL_LI_BUDGET_MB")) budget = std::max<unsigned long long>(1ull << 20, strtoull(e, nullptr, 10) << 20);
+        if (spp >= 2 && li_bytes <= budget && hipMalloc(reinterpret_cast<void**>(&li), li_bytes) == hipSuccess) {
+            (void)hipMemset(li, 0, li_bytes);
+            p.li_out = li;
+        } else {
+            li = nullptr;
+            fprintf(stderr, "--denoise: the per-sample radiance (%llu bytes) is not kept: filtering without a variance plane\n", li_bytes);
+        }
+    }
     gbl_stats st;
     auto t0 = std::chrono::steady_clock::now();
     if (stream_sampler) {
@@ -174,30 +214,81 @@ int main(int argc, char** argv) {
         fprintf(stderr, "hipMalloc failed\n");
         return 1;
     }
-    gbl_develop_params dp;
-    memset(&dp, 0, sizeof(dp));
-    dp.bloom_radius = desc->film.bloom_radius;
-    dp.bloom_weight = desc->film.bloom_weight;
-    dp.tone_mapping = is_ppm ? desc->film.tone_mapping : 0u;
-    if (gbl_film_develop(ctx, accum, &dp, floats ? rgb : nullptr, rgb8) != GBL_OK) {
-        fprintf(stderr, "gbl_film_develop failed: %s\n", gbl_last_error(ctx));
-        return 1;
+    // develops a film and writes it: the image, and the denoised film beside it
+    const auto develop_and_write = [&](const float* film, const std::string& path) -> bool {
+        gbl_develop_params dp;
+        memset(&dp, 0, sizeof(dp));
+        dp.bloom_radius = desc->film.bloom_radius;
+        dp.bloom_weight = desc->film.bloom_weight;
+        dp.tone_mapping = is_ppm ? desc->film.tone_mapping : 0u;
+        if (gbl_film_develop(ctx, film, &dp, floats ? rgb : nullptr, rgb8) != GBL_OK) {
+            fprintf(stderr, "gbl_film_develop failed: %s\n", gbl_last_error(ctx));
+            return false;
+        }
+        (void)hipDeviceSynchronize();
+        gbl_status wst;
+        if (floats) {
+            std::vector<float> host(npix * 3);
+            (void)hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDeviceToHost);
+            wst = gbl_host_write_image(path.c_str(), host.data(), info.xres, info.yres, 0);
+        } else {
+            std::vector<uint8_t> host(npix * 3);
+            (void)hipMemcpy(host.data(), rgb8, host.size(), hipMemcpyDeviceToHost);
+            wst = gbl_host_write_ppm8((is_ppm ? path : path + ".ppm").c_str(), host.data(), info.xres, info.yres);
+        }
+        if (wst != GBL_OK) {
+            fprintf(stderr, "write failed: %s\n", gbl_host_last_error());
+            return false;
+        }
+        return true;
+    };
+    if (denoise) {
+        // feature films of the very samples rendered above, the variance of the pixel mean where li was kept, the filter
+        float* work = nullptr;   // 3 feature accumulators, the denoised film, the variance plane
+        if (hipMalloc(reinterpret_cast<void**>(&work), npix * 17 * sizeof(float)) != hipSuccess) {
+            fprintf(stderr, "hipMalloc failed\n");
+            return 1;
+        }
+        (void)hipMemset(work, 0, npix * 17 * sizeof(float));
+        gbl_aov_targets tg;
+        memset(&tg, 0, sizeof(tg));
+        tg.albedo_accum = work;
+        tg.normal_accum = work + 4 * npix;
+        tg.depth_accum = work + 8 * npix;
+        float* const denoised = work + 12 * npix;
+        float* const variance = li ? work + 16 * npix : nullptr;
+        gbl_render_params ap = p;
+        ap.li_out = nullptr;
+        memset(ap.window, 0, sizeof(ap.window));
+        if (gbl_render_aov(ctx, &ap, &tg, nullptr) != GBL_OK) {
+            fprintf(stderr, "gbl_render_aov failed: %s\n", gbl_last_error(ctx));
+            return 1;
+        }
+        if (li && gbl_film_variance(ctx, li, ap.window, p.sample_per_pixel, variance, nullptr) != GBL_OK) {
+            fprintf(stderr, "gbl_film_variance failed: %s\n", gbl_last_error(ctx));
+            return 1;
+        }
+        gbl_denoise_params np;
+        memset(&np, 0, sizeof(np));
+        np.iterations = denoise;
+        np.sigma_luminance = 4.0f;
+        np.sigma_normal = 0.5f;
+        np.sigma_albedo = 0.1f;
+        np.sigma_depth = 0.1f;
+        np.demodulate = 1;
+        if (gbl_film_denoise(ctx, accum, variance, tg.albedo_accum, tg.normal_accum, tg.depth_accum, &np, denoised) != GBL_OK) {
+            fprintf(stderr, "gbl_film_denoise failed: %s\n", gbl_last_error(ctx));
+            return 1;
+        }
+        const size_t slash = out_path.rfind("/");
+        const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+        const std::string dn_path = has_ext ? out_path.substr(0, dot) + ".denoised" + ext : out_path + ".denoised";
+        if (!develop_and_write(denoised, dn_path)) return 1;
+        printf("write denoised image to : %s\n", dn_path.c_str());
+        (void)hipFree(work);
+        if (li) (void)hipFree(li);
     }
-    (void)hipDeviceSynchronize();
-    gbl_status wst;
-    if (floats) {
-        std::vector<float> host(npix * 3);
-        (void)hipMemcpy(host.data(), rgb, host.size() * sizeof(float), hipMemcpyDeviceToHost);
-        wst = gbl_host_write_image(out_path.c_str(), host.data(), info.xres, info.yres, 0);
-    } else {
-        std::vector<uint8_t> host(npix * 3);
-        (void)hipMemcpy(host.data(), rgb8, host.size(), hipMemcpyDeviceToHost);
-        wst = gbl_host_write_ppm8((is_ppm ? out_path : out_path + ".ppm").c_str(), host.data(), info.xres, info.yres);
-    }
-    if (wst != GBL_OK) {
-        fprintf(stderr, "write failed: %s\n", gbl_host_last_error());
-        return 1;
-    }
+    if (!develop_and_write(accum, out_path)) return 1;
     printf("Render Complete!\n%llu paths in %.3f s (kernel %.3f ms, %.1f Mpaths/s)\nwrite image to : %s\n",
            static_cast<unsigned long long>(st.paths), sec, st.kernel_ms, st.paths / (st.kernel_ms * 1e3), out_path.c_str());
     (void)hipFree(accum);

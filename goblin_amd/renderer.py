@@ -254,3 +254,55 @@ class HipPathTracer:
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return depth, coverage
+
+    def variance(self, li, window=None, setting=None):
+        """Variance of the pixel mean (gbl_film_variance) from the per-sample radiance ``render(want_li=True)`` returns for the
+        same window and setting: a (yres, xres) float32 tensor, 0 outside the window and where fewer than two finite
+        samples fell.  On the current stream."""
+        torch = _torch()
+        s = setting or self.scene.desc.setting
+        w = window or self.window
+        spp = _abi.host_lib().gbl_host_round_to_square(s.sample_per_pixel)
+        n = (w[1] - w[0]) * (w[3] - w[2]) * spp
+        if tuple(li.shape) != (n, 4) or li.dtype != torch.float32 or li.device != self.device or not li.is_contiguous():
+            raise ValueError("li must be a contiguous (%d, 4) float32 tensor on %s" % (n, self.device))
+        out = torch.zeros((self.info.yres, self.info.xres), dtype=torch.float32, device=self.device)
+        st = self.lib.gbl_film_variance(self.handle, li.data_ptr(), (C.c_int32 * 4)(*[int(v) for v in w]), s.sample_per_pixel,
+                                        out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return out
+
+    def denoise(self, film, variance=None, albedo=None, normal=None, depth=None, iterations=5, sigma_luminance=4.0,
+                sigma_normal=0.5, sigma_albedo=0.1, sigma_depth=0.1, demodulate=True):
+        """Edge-avoiding a-trous filter of a film (gbl_film_denoise) on the current stream.  ``film`` and the guides
+        ``albedo`` / ``normal`` / ``depth`` (render_aov's) are Films or their (yres, xres, 4) accumulator tensors, ``variance``
+        the (yres, xres) plane of ``variance()``; a guide left None drops out of the filter.  demodulate divides by the albedo
+        before filtering and multiplies back after; it is ignored without an albedo film.
+        Returns a new Film {rgb, 1} ({0, 0, 0, 0} for a pixel of weight 0 or with a non-finite input): ``normalized()`` and
+        ``develop()`` take it as they take a rendered one."""
+        torch = _torch()
+        h, w = self.info.yres, self.info.xres
+
+        def plane(t, shape, what):
+            if t is None:
+                return None
+            t = t.accum if isinstance(t, Film) else t
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s float32 tensor on %s" % (what, shape, self.device))
+            return t
+        accum = plane(film, (h, w, 4), "film")
+        var = plane(variance, (h, w), "variance")
+        guides = [plane(albedo, (h, w, 4), "albedo"), plane(normal, (h, w, 4), "normal"), plane(depth, (h, w, 4), "depth")]
+        p = _abi.gbl_denoise_params()
+        p.iterations = int(iterations)
+        p.sigma_luminance, p.sigma_normal = float(sigma_luminance), float(sigma_normal)
+        p.sigma_albedo, p.sigma_depth = float(sigma_albedo), float(sigma_depth)
+        p.demodulate = 1 if (demodulate and guides[0] is not None) else 0
+        p.stream = torch.cuda.current_stream(self.device).cuda_stream
+        out = Film(w, h, self.device)
+        st = self.lib.gbl_film_denoise(self.handle, accum.data_ptr(), var.data_ptr() if var is not None else None,
+                                       *[g.data_ptr() if g is not None else None for g in guides], C.byref(p), out.accum.data_ptr())
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return out

@@ -550,6 +550,38 @@ gbl_status gbl_render_aov(gbl_ctx* ctx, const gbl_render_params* params, const g
 /* depth_out[W*H] = x / y (IEEE divide) and coverage_out[W*H] (or NULL) = y / w of depth_accum; 0 where the denominator is 0. */
 gbl_status gbl_aov_resolve_depth(gbl_ctx* ctx, const float* depth_accum, float* depth_out, float* coverage_out, void* stream);
 
+/* Variance of the pixel mean from per-sample radiance.  li: n x 4 floats in gbl_render's li_out order --
+ * pixel-major over `window`, S entries per pixel; window and sample_per_pixel as in gbl_render_params ({0,0,0,0} or NULL =
+ * the whole sample window, S rounded up to a square).  For every window pixel inside the image, with
+ * l_k = (0.2126f r + 0.7152f g) + 0.0722f b of sample k and the samples whose l_k is not finite dropped (ImageTile::addSample's
+ * rule), m samples left:  mean = (sum l) / m,  variance_out[y * xres + x] = (sum (l - mean)^2) / (m (m - 1)) in float32, m (m - 1)
+ * formed in float32; 0 when m < 2.  Both sums run over k = 0 .. S-1 in that order, one after the other, so the plane is
+ * reproducible bit for bit.  Window pixels outside the image (the filter border) are ignored; image pixels outside the window
+ * are not written.  S < 2 is GBL_ERR_INVALID.  Under a tile shard the li entries of tiles the call does not own are zero, so
+ * their variance is 0: the planes of disjoint shards add up to the whole plane under gbl_film_allreduce-style summation.
+ * Asynchronous on `stream`. */
+gbl_status gbl_film_variance(gbl_ctx* ctx, const float* li, const int32_t window[4], int32_t sample_per_pixel,
+                             float* variance_out /* xres*yres */, void* stream);
+
+/* Edge-avoiding a-trous wavelet filter of a film, guided by the first-hit films of gbl_render_aov and by the variance of the
+ * pixel mean (DESIGN.md 4.6 states the filter operation by operation).  All inputs are complete films (with several GPUs:
+ * after gbl_film_allreduce); each guide may be NULL and its term then drops out.  Without depth_accum every pixel counts as
+ * covered.  film_out: xres*yres float4, {rgb, 1} for a valid pixel and {0,0,0,0} for an invalid one (weight 0 or a
+ * non-finite input), so gbl_film_resolve and gbl_film_develop take it unchanged; it may not overlap an input.  An invalid pixel
+ * neither contributes to nor receives from a neighbour.  A pixel whose neighbours all weigh 0 keeps its colour to within one
+ * rounding of (h c) / h.  Asynchronous on params->stream; the scratch (four float4 planes) lives in the context: calls that
+ * share a context are ordered by the caller. */
+typedef struct gbl_denoise_params {
+    int32_t iterations;                 /* 1..8 a-trous levels; level i taps at stride 2^i */
+    float sigma_luminance;              /* > 0; in standard deviations of the pixel mean when a variance plane is given */
+    float sigma_normal, sigma_albedo, sigma_depth;   /* > 0, each read only if its film is given */
+    uint32_t demodulate;                /* divide by albedo before filtering, multiply back after; needs albedo_accum */
+    void* stream;                       /* hipStream_t, NULL = default stream */
+} gbl_denoise_params;
+gbl_status gbl_film_denoise(gbl_ctx* ctx, const float* film_accum, const float* variance /* or NULL */,
+                            const float* albedo_accum, const float* normal_accum, const float* depth_accum /* each or NULL */,
+                            const gbl_denoise_params* params, float* film_out /* xres*yres float4 */);
+
 /* Device time of recent gbl_render calls, from HIP events recorded on the render stream
  * around the dominant kernel and around the whole call (no host synchronisation happens
  * inside gbl_render for this).  out[0] is the most recent call.  Blocks until those events
