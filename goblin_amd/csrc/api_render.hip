@@ -371,6 +371,7 @@ gbl_status plan_samples(gbl_ctx* ctx, const gbl_render_params* p, bool check_sch
     const DevScene& sc = ctx->scene;
     RenderArgs& ra = pl->ra;
     memset(&ra, 0, sizeof(ra));
+    ra.unit_rows = GBL_TILE;   // work items are whole tiles (plan_wave_units: the lean quad path kernels' are not)
     if (p->integrator != GBL_INTEGRATOR_PATH && p->integrator != GBL_INTEGRATOR_AO && p->integrator != GBL_INTEGRATOR_WHITTED)
         return fail(ctx, GBL_ERR_INVALID, "unknown integrator");
     if (p->sample_per_pixel < 1 || p->max_ray_depth < 1) return fail(ctx, GBL_ERR_INVALID, "sample_per_pixel and max_ray_depth must be >= 1");
@@ -538,6 +539,34 @@ gbl_status plan_render(gbl_ctx* ctx, const gbl_render_params* p, float* film_acc
     if (pl->stream_mode && !pl->defer)
         return fail(ctx, GBL_ERR_UNSUPPORTED, "GBL_SAMPLES_STREAM keeps 16 bytes per camera sample of the call: render this window in smaller pieces");
     return GBL_OK;
+}
+
+// The lean quad path kernels of the native sampler take their work wave by wave (render_kernels.h wave_take), so their launch
+// is planned in units per resident WAVE where plan_render plans items per resident workgroup: a unit is a band of rows of a
+// tile x a chunk of samples, at most 512 paths (8 per lane) -- one row of 64-sample chunks on the headline frame.  A wave no
+// longer shares an item's tail with three others, so the unit is what balances the launch: measured on configs[1] 4096 /
+// 2048 / 1024 / 512 / 256 / 128 paths -> 56.0 / 44.5 / 38.2 / 37.3 / 37.5 / 38.2 ms (DESIGN_HISTORY, "Wave-owned work units").  Chunks stay at <= 64
+// samples as before (64 consecutive path ids of a unit are then the consecutive samples of one pixel: a wave's rays leave
+// one pixel); a launch with fewer than ~16 units per resident wave halves the band down to one row first and the chunk,
+// down to 4 samples, after.
+void plan_wave_units(const gbl_ctx* ctx, Plan* pl) {
+    RenderArgs& ra = pl->ra;
+    int chunks = 1, rows = GBL_TILE;
+    while (ra.spp / chunks > 64 && ra.spp % (chunks * 2) == 0) chunks *= 2;
+    while (rows > 1 && GBL_TILE * rows * (ra.spp / chunks) > 512) rows /= 2;
+    const uint64_t want_units = 16ull * ctx->num_cus * GBL_PT_WAVES * 4;
+    while (static_cast<uint64_t>(ra.local_tiles) * chunks * (GBL_TILE / rows) < want_units) {
+        if (rows > 1)
+            rows /= 2;
+        else if (ra.spp / chunks > 4 && ra.spp % (chunks * 2) == 0)
+            chunks *= 2;
+        else
+            break;
+    }
+    ra.chunks = chunks;
+    ra.chunk_spp = ra.spp / chunks;
+    ra.unit_rows = rows;
+    pl->n_items = static_cast<uint64_t>(ra.local_tiles) * chunks * (GBL_TILE / rows);
 }
 
 gbl_status gbl_render_impl(gbl_ctx* ctx, const gbl_render_params* p, float* film_accum, gbl_stats* stats, const RenderKnobs& knobs);
@@ -730,7 +759,7 @@ gbl_status primary_pass(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl, cons
         return GBL_OK;
     gbl_status st = grow(ctx, ctx->prim_hits, pl.entries * 20, "primary hits");
     if (st != GBL_OK) return st;
-    // one word per work item of the path kernel
+    // one word per work item of the path kernel (render_megakernel has planned its wave-owned units by now)
     if ((st = grow(ctx, ctx->prim_items, pl.n_items * sizeof(uint32_t), "primary items")) != GBL_OK) return st;
     HIP_TRY(ctx, hipMemsetAsync(ctx->prim_items.p, 0, pl.n_items * sizeof(uint32_t), stream));
     ra.prim_items = static_cast<uint32_t*>(ctx->prim_items.p);
@@ -764,6 +793,8 @@ void print_counters(const unsigned long long* h, bool phase_clock) {
                     "%.1f%% + migrate %.1f%% + quad %.1f%% | rest (shading, regeneration, item fetch) %.1f%% | dense iterations %llu, quad iterations %llu, "
                     "wave ticks %llu\n", 100 * h[0] / k, 100 * h[1] / k, 100 * h[2] / k, 100 * h[3] / k, 100 * h[4] / k, 100 * h[5] / k, 100 * h[6] / k, 100 * h[7] / k,
                     100 * (k - h[0] - h[4]) / k, h[9], h[10], h[8]);
+            fprintf(stderr, "phase clock, item loop: iterations run with lanes that have nothing left to take (drain) %.2f%%, between an item's last iteration and the next "
+                    "one's first (barriers, fetch) %.2f%%\n", 100 * h[30] / k, 100 * h[31] / k);
             fprintf(stderr, "phase clock, dense loop: interior blocks %llu (%.0f ticks, %.1f lanes each, %.1f%% of the kernel), leaf / instance blocks %llu (%.0f ticks, %.1f lanes, %.1f%%)\n",
                     h[13], h[13] ? double(h[11]) / h[13] : 0.0, h[13] ? double(h[15]) / h[13] : 0.0, 100 * h[11] / k, h[14], h[14] ? double(h[12]) / h[14] : 0.0,
                     h[14] ? double(h[16]) / h[14] : 0.0, 100 * h[12] / k);
@@ -847,6 +878,11 @@ gbl_status render_megakernel(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl,
             kernel = k_quad;
             lds = lds_quad;
             if ((st = allow_lds(ctx, kernel, lds)) != GBL_OK) return st;
+            if (!stream_mode && !ao && gbl_quad_wave_units()) {   // wave-owned units: four waves to a workgroup, never more waves than units
+                plan_wave_units(ctx, &pl);
+                grid64 = std::min<uint64_t>((pl.n_items + GBL_BLOCK / 64 - 1) / (GBL_BLOCK / 64), static_cast<uint64_t>(ctx->num_cus) * pl.per_cu);
+                grid = dim3(static_cast<unsigned>(grid64));
+            }
             bool primary = false;
             if ((st = primary_pass(ctx, p, pl, knobs, stream, &primary)) != GBL_OK) return st;
             if (primary) {

@@ -264,6 +264,7 @@ struct RenderArgs {
     int32_t local_tiles;        // number of tiles this launch owns
     int32_t chunks;             // each tile's spp split in `chunks` work items
     int32_t chunk_spp;
+    int32_t unit_rows;          // rows of a tile per work item: GBL_TILE (whole tiles) but for the lean quad path kernels' wave-owned units (8, 4, 2 or 1)
     uint32_t seed_key;
     uint32_t russian_roulette;
     int32_t bssrdf_n;           // BSSRDFSampleIndex::samplesNum: roundToSquare(bssrdf_sample_num)

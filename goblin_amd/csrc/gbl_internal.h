@@ -107,6 +107,7 @@ gbl_render_kernel gbl_kernel_path_stream_quad(void);
 gbl_render_kernel gbl_kernel_ao_quad(bool exact_ties);
 void gbl_launch_primary(const DevScene& sc, const RenderArgs& ra, bool exact_ties, float4* prim_hit, int32_t* prim_inst, unsigned blocks, hipStream_t stream);   // kernels/packet.h
 uint32_t gbl_quad_lds_words(void);          // LDS words of the quads' records, in the film tile's place
+bool gbl_quad_wave_units(void);             // the quad path kernels take wave-owned work units (not in a -DGBL_WG_ITEMS build)
 // kernels_stream.hip: the same two under GBL_SAMPLES_STREAM (kernels/stream.h)
 gbl_render_kernel gbl_kernel_path_stream(bool stats, bool ext);
 gbl_render_kernel gbl_kernel_ao_stream(bool ext);

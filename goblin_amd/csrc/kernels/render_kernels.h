@@ -3,7 +3,8 @@
 // by regenerating camera paths from an LDS counter as soon as their previous
 // path ends (wave ballot + prefix popcount).  Radiance is splatted through the
 // reconstruction filter into an LDS film tile (8x8 pixels + halo) with LDS float
-// atomics and flushed to the HBM film once per item.
+// atomics and flushed to the HBM film once per item.  (The lean quad path kernels keep
+// no film tile and take their work wave by wave instead: wave_take.)
 //
 // Replaces RenderTask::run + PathTracer::Li / AORenderer::Li + ImageTile::addSample
 // (GoblinRenderer.cpp:29-52, GoblinPathtracer.cpp:50-179, GoblinAO.cpp:12-37,
@@ -27,19 +28,38 @@
 #include "vecmath.h"
 
 struct ItemInfo {
-    int px0, py0, tw, th;   // tile origin and clipped size in pixels
+    int px0, py0, tw, th;   // origin and clipped size in pixels of the item's rows of its tile
     int k0;                 // first sample index of this chunk
-    int paths;              // tw * th * chunk_spp
+    int paths;              // tw * th * chunk_spp (0: a band of rows an edge tile's clipping leaves empty)
 };
 
+// The work items of a launch: (owned tile, chunk of chunk_spp samples, band of unit_rows rows of the tile), the band running
+// fastest.  Every kernel but the lean quad path kernels takes whole tiles (unit_rows == GBL_TILE: one band).  item_layout is
+// the numbering, for the kernel that takes items (decode_item) and for the primary pass that marks them (item_index).
+struct ItemLayout {
+    uint32_t bands, per_tile;   // bands of a tile; items of a tile
+};
+__device__ __forceinline__ ItemLayout item_layout(const RenderArgs& ra) {
+    ItemLayout l;
+    l.bands = static_cast<uint32_t>(GBL_TILE / ra.unit_rows);
+    l.per_tile = static_cast<uint32_t>(ra.chunks) * l.bands;
+    return l;
+}
+// The item of sample k of a pixel in row `row` (0 .. 7) of owned tile lt
+__device__ __forceinline__ uint32_t item_index(const RenderArgs& ra, uint32_t lt, uint32_t k, uint32_t row) {
+    const ItemLayout l = item_layout(ra);
+    return lt * l.per_tile + (k / static_cast<uint32_t>(ra.chunk_spp)) * l.bands + row / static_cast<uint32_t>(ra.unit_rows);
+}
 __device__ __forceinline__ ItemInfo decode_item(const RenderArgs& ra, uint32_t item) {
     ItemInfo it;
-    uint32_t tile = ra.shard_index + (item / ra.chunks) * ra.shard_count, chunk = item % ra.chunks;
+    const ItemLayout l = item_layout(ra);
+    const uint32_t in_tile = item % l.per_tile, chunk = in_tile / l.bands, band = in_tile % l.bands;
+    uint32_t tile = ra.shard_index + (item / l.per_tile) * ra.shard_count;
     int tx = tile % ra.tiles_x, ty = tile / ra.tiles_x;
     it.px0 = ra.window[0] + GBL_TILE * tx;
-    it.py0 = ra.window[2] + GBL_TILE * ty;
+    it.py0 = ra.window[2] + GBL_TILE * ty + static_cast<int>(band) * ra.unit_rows;
     it.tw = min(GBL_TILE, ra.window[1] - it.px0);
-    it.th = min(GBL_TILE, ra.window[3] - it.py0);
+    it.th = max(0, min(ra.unit_rows, ra.window[3] - it.py0));
     it.k0 = chunk * ra.chunk_spp;
     it.paths = it.tw * it.th * ra.chunk_spp;
     return it;
@@ -302,6 +322,45 @@ __device__ __forceinline__ int wave_fetch(bool want, uint32_t* next_path) {
     return want ? static_cast<int>(base + rank) : -1;
 }
 
+// The lean quad path kernels' fetch: the wave owns a work unit `it` (decode_item: a band of rows of a tile x a chunk of samples,
+// taken from the launch's global counter by one lane) and hands out its path ids [pos, it.paths) to its idle lanes; `it` and
+// `pos` are wave-uniform.  A unit that runs out is replaced within the call, so a round of regeneration (the caller loops while
+// lanes are idle) fills a wave's lanes across unit boundaries and no lane waits for the others' paths to end: lanes of one wave
+// may hold paths of two units, everything a path needs after regeneration being per lane.  Units the primary pass found
+// nothing in (PRIM) cost their word's read, empty bands of clipped tiles nothing more.  Returns the lane's path id in `it`, or
+// -1: not idle, or beyond this unit's end (the caller asks again), or -- `exhausted`, for the whole wave at once -- the
+// counter has passed the launch's last unit.
+// `it`, `pos` and `exhausted` are the caller's locals, wave-uniform by construction: they change only here, under conditions made
+// of ballots and of the unit number, which one lane takes and readfirstlane hands to all.
+template <bool PRIM>
+__device__ __forceinline__ int wave_take(const RenderArgs& ra, uint32_t n_units, bool idle, ItemInfo& it, uint32_t& pos, bool& exhausted) {
+    const unsigned long long mask = __ballot(idle);
+    if (mask == 0ull) return -1;
+    const int lane = threadIdx.x & 63;
+    while (pos >= static_cast<uint32_t>(it.paths)) {
+        uint32_t unit = 0;
+        if (lane == __ffsll(static_cast<long long>(__ballot(true))) - 1) unit = atomicAdd(ra.work_counter, 1u);
+        unit = __builtin_amdgcn_readfirstlane(unit);
+        if (unit >= n_units) {
+            exhausted = true;
+            return -1;
+        }
+        if (PRIM && ra.prim_items[unit] == 0u) continue;
+        const ItemInfo d = decode_item(ra, unit);   // (readfirstlane: kept in scalar registers)
+        it.px0 = __builtin_amdgcn_readfirstlane(d.px0);
+        it.py0 = __builtin_amdgcn_readfirstlane(d.py0);
+        it.tw = __builtin_amdgcn_readfirstlane(d.tw);
+        it.th = __builtin_amdgcn_readfirstlane(d.th);
+        it.k0 = __builtin_amdgcn_readfirstlane(d.k0);
+        it.paths = __builtin_amdgcn_readfirstlane(d.paths);
+        pos = 0u;
+    }
+    const uint32_t base = pos;
+    pos = min(static_cast<uint32_t>(it.paths), base + static_cast<uint32_t>(__popcll(mask)));
+    const uint32_t id = base + static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
+    return idle && id < static_cast<uint32_t>(it.paths) ? static_cast<int>(id) : -1;
+}
+
 __device__ __forceinline__ void accumulate_stats(const RenderArgs& ra, const LaneCounters& c, uint32_t paths) {
     unsigned long long v[25] = {paths, c.ext, c.shadow, c.nodes, c.tris, c.splats, c.dims, c.int_lane, c.int_wave, c.oth_lane, c.oth_wave};
     for (int i = 0; i < 7; ++i) {
@@ -516,6 +575,14 @@ __device__ void stream_medium_phase(const DevScene& sc, const RenderArgs& ra, St
 // EXACT: the native sampler's lean kernels leave the reference's exact-t tie rule and reachability test out (trace.h: +16 % on
 // configs[1] for the few rays per 10^6 they decide); gbl_render_params.exact_ties selects the instantiations that follow them.
 // Every other build does anyway: replay, stream, instrumented, and the EXT builds of the feature scenes.
+// The lean quad path kernels of the native sampler take their work wave by wave (wave_take); -DGBL_WG_ITEMS builds them with the
+// workgroup's item loop every other kernel has, for the A/B (a variant library, tools/build_variant.py: the host asks
+// gbl_quad_wave_units() which one it got).
+#ifdef GBL_WG_ITEMS
+#define GBL_WAVE_UNITS false
+#else
+#define GBL_WAVE_UNITS true
+#endif
 #ifdef GBL_STREAM_TM   // measurement builds: the stream sampler's phase clock in every instantiation (tools/stream_probe.py)
 #define GBL_STREAM_TM_ON true
 #else
@@ -526,6 +593,7 @@ template <int SAMPLER, bool STATS, bool EXT, bool QUAD = false, bool EXACT = fal
 //  held to the lean build's 168 registers they spilled 300-1200 of them; two waves per SIMD (256 registers) hold them)
 __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void path_trace_kernel(DevScene sc, RenderArgs ra) {
     constexpr bool REPLAY = SAMPLER != GBL_SRC_NATIVE, STREAM = SAMPLER == GBL_SRC_STREAM, TIES = REPLAY || STATS || EXACT || EXT;
+    constexpr bool WAVE = QUAD && SAMPLER == GBL_SRC_NATIVE && GBL_WAVE_UNITS;   // wave-owned work units (below); else the workgroup's item loop
     extern __shared__ __align__(16) unsigned char smem[];
     const int tp = GBL_TILE + 2 * sc.film.halo;
     float* tile = reinterpret_cast<float*>(smem);
@@ -568,26 +636,35 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
     LaneCounters cnt = {};
 #ifdef GBL_PHASE_CLOCK
     const unsigned long long pc_k0 = __builtin_amdgcn_s_memtime();
+    unsigned long long pc_drain = 0ull, pc_between = 0ull, pc_iter = 0ull, pc_item_end = 0ull;
+    bool pc_draining = false, pc_first = true;
 #endif
     uint32_t paths_done = 0;
-    const uint32_t n_items = static_cast<uint32_t>(ra.local_tiles) * ra.chunks;
+    const uint32_t n_items = static_cast<uint32_t>(ra.local_tiles) * item_layout(ra).per_tile;
     const int sub_w = ra.window[1] - ra.window[0];
     const int full_w = sc.film.window[1] - sc.film.window[0];
     unsigned long long stream_tm[5] = {0ull, 0ull, 0ull, 0ull, 0ull};   // instrumented STREAM builds: phase ticks (emit, permute, assemble, paths, skip)
 
+    // WAVE: no film tile to zero and flush, so nothing here needs the workgroup to agree once the hot nodes are published: each
+    // wave owns the unit it took from the global counter, hands its paths to its idle lanes, takes the next unit in the same
+    // regeneration round when that one runs out (wave_take), and leaves on its own.  No barrier below this one.
+    if constexpr (WAVE) __syncthreads();
     for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            ctrl[0] = atomicAdd(ra.work_counter, 1u);
-            ctrl[1] = 0u;
+        ItemInfo tile_item = {};   // WAVE: no unit yet (paths == 0): the first regeneration round takes one
+        if constexpr (!WAVE) {
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                ctrl[0] = atomicAdd(ra.work_counter, 1u);
+                ctrl[1] = 0u;
+            }
+            if (!QUAD && !ra.li_defer)
+                for (int i = threadIdx.x; i < 4 * tp * tp; i += GBL_BLOCK) tile[i] = 0.0f;
+            __syncthreads();
+            const uint32_t item = ctrl[0];
+            if (item >= n_items) break;
+            if (PRIM && ra.prim_items[item] == 0u) continue;   // (uniform) every camera ray of the item left the scene: the pass has written its Blacks
+            tile_item = decode_item(ra, item);
         }
-        if (!QUAD && !ra.li_defer)
-            for (int i = threadIdx.x; i < 4 * tp * tp; i += GBL_BLOCK) tile[i] = 0.0f;
-        __syncthreads();
-        const uint32_t item = ctrl[0];
-        if (item >= n_items) break;
-        if (PRIM && ra.prim_items[item] == 0u) continue;   // (uniform) every camera ray of the item left the scene: the pass has written its Blacks
-        const ItemInfo tile_item = decode_item(ra, item);
         const int tx0 = tile_item.px0 - sc.film.halo, ty0 = tile_item.py0 - sc.film.halo;
         if constexpr (STREAM) {
             // RNGImp of this tile's RenderTask: seeded with the tile's rand() value (row-major over the FULL sample window)
@@ -615,7 +692,8 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
 
         PathState ps;
         bool active = false;
-        bool exhausted = false;
+        bool exhausted = false;   // WAVE: wave-uniform
+        uint32_t unit_pos = 0;    // WAVE: next path id of the wave's unit `it` (wave-uniform)
         SampleSource src;
         src.spp = ra.spp;
         src.root = ra.root;
@@ -625,54 +703,79 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
         float image_x = 0.0f, image_y = 0.0f;
         uint32_t out_index = 0;
 
+        // WAVE, termination: the loop is left exactly when no lane holds a path after a round of regeneration.  A round ends
+        // only when no lane is idle: every lane got a path, or wave_take saw the global counter at or past the unit count and
+        // set `exhausted` for the whole wave -- the counter only grows, so nothing is left for this wave to take, and every unit
+        // below the count was taken by exactly one wave, which hands out each of its path ids once before it asks for another
+        // unit.  Each unit is finite and each path ends within max_depth bounces, so the wave gets there.  A wave that finds
+        // no unit at all leaves from its first round, before either query has touched the LDS stacks or the slab.
         for (;;) {
+#ifdef GBL_PHASE_CLOCK
+            if constexpr (QUAD && !STATS) {   // (see the end of the kernel)
+                const unsigned long long now = __builtin_amdgcn_s_memtime();
+                if (pc_draining) pc_drain += now - pc_iter;
+                if (pc_item_end != 0ull && pc_first) pc_between += now - pc_item_end;
+                pc_first = false;
+                pc_iter = now;
+                pc_draining = __ballot(exhausted) != 0ull;
+            }
+#endif
             // ---- regeneration: idle lanes start a new camera path
             // (PRIM: below, after the bounce in flight is closed -- a path starts at the hit the primary pass found for it)
-            int fetched = PRIM ? -1 : wave_fetch(!active && !exhausted, ctrl + 1);
-            if (!PRIM && !active && !exhausted) {
-                if (fetched >= 0 && fetched < it.paths) {
-                    int pix = fetched / ra.chunk_spp;
-                    src.k = static_cast<uint32_t>(it.k0 + fetched % ra.chunk_spp);
-                    int px = it.px0 + pix % it.tw, py = it.py0 + pix / it.tw;
-                    out_index = static_cast<uint32_t>((py - ra.window[2]) * sub_w + (px - ra.window[0])) * ra.spp + src.k;
-                    if (REPLAY) {
-                        src.rec = STREAM ? scx.recs + static_cast<size_t>(src.k) * ra.dims : ra.replay + static_cast<size_t>(out_index) * ra.dims;
-                        image_x = src.rec[0];
-                        image_y = src.rec[1];
-                        if (STREAM) {
-                            ra.image_xy[2 * static_cast<size_t>(out_index)] = image_x;
-                            ra.image_xy[2 * static_cast<size_t>(out_index) + 1] = image_y;
-                        }
+            int fetched = -1;
+            if constexpr (!PRIM) {
+                for (;;) {   // a round of regeneration; WAVE: one round per unit the idle lanes are filled from
+                    const bool idle = !active && !exhausted;
+                    if constexpr (WAVE) {
+                        if (__ballot(idle) == 0ull) break;
+                        fetched = wave_take<false>(ra, n_items, idle, it, unit_pos, exhausted);   // (-1 beyond the unit's end: the next round's unit)
                     } else {
-                        uint32_t pixel = static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0]));
-                        src.pixel_key = nat_mix(ra.seed_key, pixel);
-                        float u, v;
-                        src.native_2d(0u, 1u, 0u, false, &u, &v);
-                        image_x = px + u;
-                        image_y = py + v;
+                        fetched = wave_fetch(idle, ctrl + 1);
+                        if (idle && (fetched < 0 || fetched >= it.paths)) exhausted = true;
                     }
-                    float lens_u1 = 0.0f, lens_u2 = 0.0f;
-                    if (EXT && sc.camera.lens_radius != 0.0f) {
+                    if (idle && !exhausted && fetched >= 0) {
+                        int pix = fetched / ra.chunk_spp;
+                        src.k = static_cast<uint32_t>(it.k0 + fetched % ra.chunk_spp);
+                        int px = it.px0 + pix % it.tw, py = it.py0 + pix / it.tw;
+                        out_index = static_cast<uint32_t>((py - ra.window[2]) * sub_w + (px - ra.window[0])) * ra.spp + src.k;
                         if (REPLAY) {
-                            lens_u1 = src.rec[2];
-                            lens_u2 = src.rec[3];
+                            src.rec = STREAM ? scx.recs + static_cast<size_t>(src.k) * ra.dims : ra.replay + static_cast<size_t>(out_index) * ra.dims;
+                            image_x = src.rec[0];
+                            image_y = src.rec[1];
+                            if (STREAM) {
+                                ra.image_xy[2 * static_cast<size_t>(out_index)] = image_x;
+                                ra.image_xy[2 * static_cast<size_t>(out_index) + 1] = image_y;
+                            }
                         } else {
-                            src.native_2d(1u, 1u, 0u, true, &lens_u1, &lens_u2);
+                            uint32_t pixel = static_cast<uint32_t>((py - sc.film.window[2]) * full_w + (px - sc.film.window[0]));
+                            src.pixel_key = nat_mix(ra.seed_key, pixel);
+                            float u, v;
+                            src.native_2d(0u, 1u, 0u, false, &u, &v);
+                            image_x = px + u;
+                            image_y = py + v;
                         }
+                        float lens_u1 = 0.0f, lens_u2 = 0.0f;
+                        if (EXT && sc.camera.lens_radius != 0.0f) {
+                            if (REPLAY) {
+                                lens_u1 = src.rec[2];
+                                lens_u2 = src.rec[3];
+                            } else {
+                                src.native_2d(1u, 1u, 0u, true, &lens_u1, &lens_u2);
+                            }
+                        }
+                        camera_ray<EXT>(sc.camera, image_x, image_y, lens_u1, lens_u2, &ps.o, &ps.d, &ps.mint);
+                        ps.throughput = f3(1.0f, 1.0f, 1.0f);
+                        ps.Li = f3(0.0f, 0.0f, 0.0f);
+                        ps.bounce = -1;
+                        ps.punch = false;
+                        ps.first = true;
+                        ps.path = fetched;
+                        path_draws = 0;
+                        prim_t = INFINITY;
+                        active = true;
+                        if (STATS) cnt.dims += 2;
                     }
-                    camera_ray<EXT>(sc.camera, image_x, image_y, lens_u1, lens_u2, &ps.o, &ps.d, &ps.mint);
-                    ps.throughput = f3(1.0f, 1.0f, 1.0f);
-                    ps.Li = f3(0.0f, 0.0f, 0.0f);
-                    ps.bounce = -1;
-                    ps.punch = false;
-                    ps.first = true;
-                    ps.path = fetched;
-                    path_draws = 0;
-                    prim_t = INFINITY;
-                    active = true;
-                    if (STATS) cnt.dims += 2;
-                } else {
-                    exhausted = true;
+                    if constexpr (!WAVE) break;
                 }
             }
             if (!PRIM && __ballot(active) == 0ull) break;
@@ -800,11 +903,16 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                 for (;;) {
                     const bool idle = !active && !exhausted;
                     if (__ballot(idle) == 0ull) break;
-                    fetched = wave_fetch(idle, ctrl + 1);
-                    if (!idle) continue;
-                    if (fetched < 0 || fetched >= it.paths) {
-                        exhausted = true;
-                        continue;
+                    if constexpr (WAVE) {
+                        fetched = wave_take<true>(ra, n_items, idle, it, unit_pos, exhausted);
+                        if (fetched < 0) continue;   // not idle; or beyond the unit's end: the next round's unit
+                    } else {
+                        fetched = wave_fetch(idle, ctrl + 1);
+                        if (!idle) continue;
+                        if (fetched < 0 || fetched >= it.paths) {
+                            exhausted = true;
+                            continue;
+                        }
                     }
                     const int pix = fetched / ra.chunk_spp;
                     src.k = static_cast<uint32_t>(it.k0 + fetched % ra.chunk_spp);
@@ -1033,6 +1141,17 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
             if (STATS || GBL_STREAM_TM_ON) stream_tm[4] += wall_clock64() - stream_t0;
         }
         }   // sub
+#ifdef GBL_PHASE_CLOCK
+        if constexpr (QUAD && !STATS) {
+            pc_item_end = __builtin_amdgcn_s_memtime();
+            if (pc_draining) pc_drain += pc_item_end - pc_iter;
+            pc_draining = false;
+            pc_first = true;
+        }
+#endif
+        // WAVE: the one pass above took units until the launch ran out of them, so the outer loop, tile_item, tx0 / ty0 and the
+        // `sub` loop are scaffolding that runs once, and the barrier and flush_tile below are never reached (nor is ctrl[1] used)
+        if constexpr (WAVE) break;
         __syncthreads();
         if (!ra.li_defer) flush_tile(sc.film, tile, tx0, ty0, tp, ra.film);
     }
@@ -1043,6 +1162,10 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
     if (QUAD && !STATS && (threadIdx.x & 63) == 0) {   // measurement build: one lane per wave reports its phase ticks
         cnt.pc[8] = __builtin_amdgcn_s_memtime() - pc_k0;
         for (int i = 0; i < 24; ++i) atomicAdd(ra.stats + i, cnt.pc[i]);
+        // the item loop's cost: ticks of the iterations run while some lane had nothing left to take (the drain), and ticks
+        // between an item's last iteration and the next one's first (the barriers and the fetch; none with wave-owned units)
+        atomicAdd(ra.stats + 30, pc_drain);
+        atomicAdd(ra.stats + 31, pc_between);
     }
 #endif
 }

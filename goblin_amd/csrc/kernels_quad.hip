@@ -16,6 +16,9 @@ gbl_render_kernel gbl_kernel_ao_quad(bool exact_ties) {
     return exact_ties ? ao_kernel<GBL_SRC_NATIVE, false, false, true, true> : ao_kernel<GBL_SRC_NATIVE, false, false, true>;
 }
 uint32_t gbl_quad_lds_words(void) { return GBL_QUAD_LDS_WORDS; }
+// Whether the path kernels above take wave-owned work units (render_kernels.h wave_take; not in a -DGBL_WG_ITEMS build): the host
+// then plans units instead of whole-tile items (api_render.hip plan_wave_units)
+bool gbl_quad_wave_units(void) { return GBL_WAVE_UNITS; }
 
 // The primary pass: every camera ray of the call, one wave per (pixel, 64 samples of it), traced as a packet (kernels/packet.h) --
 // the 64 rays start at the camera and pass through one pixel, so they meet the same nodes in the same order.  Writes the hit of
@@ -59,8 +62,8 @@ __global__ __launch_bounds__(GBL_BLOCK) void primary_kernel(DevScene sc, RenderA
                 // PathTracer::Li of a camera ray that left the scene: Black (:58-66, no image based light in the lean builds) ...
                 reinterpret_cast<float4*>(ra.li_defer)[out_index] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
             } else {
-                // ... and the path kernel's work item (owned tile x chunk of samples) of every other sample has something to do
-                ra.prim_items[lt * ra.chunks + k / static_cast<uint32_t>(ra.chunk_spp)] = 1u;
+                // ... and the path kernel's work item (render_kernels.h item_index) of every other sample has something to do
+                ra.prim_items[item_index(ra, lt, k, pix / 8u)] = 1u;
             }
         }
     }
