@@ -163,6 +163,14 @@ class gbl_denoise_params(C.Structure):
                 ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("demodulate", C.c_uint32), ("stream", C.c_void_p)]
 
 
+class gbl_temporal_params(C.Structure):
+    _fields_ = [("prev_camera", gbl_camera), ("alpha_min", C.c_float), ("max_history", C.c_float), ("sigma_depth", C.c_float),
+                ("cos_normal", C.c_float), ("reserved", C.c_uint32), ("stream", C.c_void_p)]
+
+
+GBL_HISTORY_FLOATS_PER_PIXEL = 12
+
+
 class gbl_info(C.Structure):
     _fields_ = [("xres", C.c_int32), ("yres", C.c_int32), ("window", C.c_int32 * 4), ("blas_nodes", C.c_uint64),
                 ("tlas_nodes", C.c_uint64), ("triangles", C.c_uint64), ("instances", C.c_uint64),
@@ -176,7 +184,7 @@ HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "
                 "gbl_host_bloom", "gbl_host_tone_map", "gbl_host_write_ppm", "gbl_host_write_ppm8", "gbl_host_write_exr", "gbl_host_write_image",
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
                "gbl_aov_resolve_depth", "gbl_film_variance", "gbl_film_denoise", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
@@ -266,6 +274,10 @@ def hip_lib():
         lib.gbl_film_variance.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]
         lib.gbl_film_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(gbl_denoise_params), C.c_void_p]
+        lib.gbl_film_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(gbl_temporal_params), C.c_void_p, C.c_void_p]
+        lib.gbl_update_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
+        lib.gbl_get_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
         lib.gbl_get_info.argtypes = [C.c_void_p, C.POINTER(gbl_info)]
         lib.gbl_get_timings.argtypes = [C.c_void_p, C.c_int, C.POINTER(gbl_timing)]
         lib.gbl_selftest_sincos.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -214,6 +215,9 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
     sc.volume = packed.volume;
     sc.camera = packed.camera;
     sc.film = packed.film;
+    ctx->h_camera = desc->camera;
+    ctx->h_film = desc->film;
+    ctx->scene_extended = packed.scene_extended;
     if ((st = device_alloc(ctx, sizeof(uint32_t), "work counter", reinterpret_cast<void**>(&ctx->work_counter))) != GBL_OK) return bail(st);
     if ((st = device_alloc(ctx, 32 * sizeof(unsigned long long), "stats", reinterpret_cast<void**>(&ctx->stats))) != GBL_OK) return bail(st);
     if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
@@ -311,12 +315,39 @@ gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, co
     return gbl_guard([&] { return gbl_update_instances_impl(ctx, first, count, to_world); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 
+// Host only: the camera travels to every kernel by value inside DevScene, so nothing on the device changes here and work
+// already queued keeps the camera it was launched with.
+static gbl_status gbl_update_camera_impl(gbl_ctx* ctx, const gbl_camera* camera) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!camera) return fail(ctx, GBL_ERR_INVALID, "gbl_update_camera: camera is NULL");
+    if (camera->type > GBL_CAMERA_ORTHOGRAPHIC) return fail(ctx, GBL_ERR_INVALID, "gbl_update_camera: type: unknown camera type");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(camera->position[k])) return fail(ctx, GBL_ERR_INVALID, "gbl_update_camera: position is not finite");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(camera->orientation[k])) return fail(ctx, GBL_ERR_INVALID, "gbl_update_camera: orientation is not finite");
+    if (!std::isfinite(camera->fov_degrees)) return fail(ctx, GBL_ERR_INVALID, "gbl_update_camera: fov_degrees is not finite");
+    pack_camera(*camera, ctx->h_film, &ctx->scene.camera);
+    ctx->scene.extended = (ctx->scene_extended || camera_extended(*camera)) ? 1 : 0;
+    ctx->h_camera = *camera;
+    ctx->auto_rays_per_path.clear();   // the pilot's rays per path belong to the old view: AUTO measures again
+    return GBL_OK;
+}
+gbl_status gbl_update_camera(gbl_ctx* ctx, const gbl_camera* camera) {
+    return gbl_guard([&] { return gbl_update_camera_impl(ctx, camera); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+gbl_status gbl_get_camera(const gbl_ctx* ctx, gbl_camera* out) {
+    if (!ctx || !out) return GBL_ERR_INVALID;
+    *out = ctx->h_camera;
+    return GBL_OK;
+}
+
 void gbl_destroy(gbl_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (void* p : ctx->allocations) (void)hipFree(p);
     for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->aov, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
-                       &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter, &ctx->denoise})
+                       &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter, &ctx->denoise, &ctx->temporal})
         if (b->p) (void)hipFree(b->p);
     if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
     if (ctx->wf_ev_shade) (void)hipEventDestroy(ctx->wf_ev_shade);

@@ -1,13 +1,16 @@
 // libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): what happens to a film after the render calls --
-// gbl_film_resolve, gbl_film_develop, gbl_film_variance, gbl_film_denoise and the RCCL reduce of gbl_film_allreduce.
+// gbl_film_resolve, gbl_film_develop, gbl_film_variance, gbl_film_denoise, gbl_film_accumulate and the RCCL reduce of
+// gbl_film_allreduce.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 
 #include "gbl_host.h"
+#include "scene_prep.h"
 
 extern "C" {
 
@@ -156,6 +159,74 @@ static gbl_status gbl_film_denoise_impl(gbl_ctx* ctx, const float* film_accum, c
 gbl_status gbl_film_denoise(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* albedo_accum, const float* normal_accum,
                             const float* depth_accum, const gbl_denoise_params* params, float* film_out) {
     return gbl_guard([&] { return gbl_film_denoise_impl(ctx, film_accum, variance, albedo_accum, normal_accum, depth_accum, params, film_out); },
+                     [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+// Reprojected temporal accumulation (kernels/temporal.h): prepare the current frame, then one kernel that gathers the history
+// and writes every output.
+static gbl_status gbl_film_accumulate_impl(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* normal_accum, const float* depth_accum,
+                                           const float* history_in, float* history_out, const gbl_temporal_params* p, float* film_out,
+                                           float* variance_out) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!film_accum) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: film_accum is NULL");
+    if (!depth_accum) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: depth_accum is NULL");
+    if (!history_out) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: history_out is NULL");
+    if (!p) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: params is NULL");
+    if (!film_out) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: film_out is NULL");
+    if (!std::isfinite(p->alpha_min) || !(p->alpha_min > 0.0f) || p->alpha_min > 1.0f)
+        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: alpha_min must be in (0, 1]");
+    if (!std::isfinite(p->max_history) || !(p->max_history >= 1.0f)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: max_history must be finite and >= 1");
+    if (!std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.0f)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: sigma_depth must be finite and > 0");
+    if (normal_accum && (!std::isfinite(p->cos_normal) || p->cos_normal < -1.0f || p->cos_normal > 1.0f))
+        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: cos_normal must be in [-1, 1]");
+    if (history_in && p->prev_camera.type > GBL_CAMERA_ORTHOGRAPHIC)
+        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: prev_camera.type: unknown camera type");
+    const int width = ctx->info.xres, height = ctx->info.yres, n = width * height;
+    const uint64_t film_bytes = static_cast<uint64_t>(n) * 4 * sizeof(float), plane_bytes = film_bytes / 4;
+    const uint64_t history_bytes = static_cast<uint64_t>(n) * GBL_HISTORY_FLOATS_PER_PIXEL * sizeof(float);
+    if (overlaps(history_out, history_bytes, history_in, history_bytes))
+        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: history_out may not overlap history_in (the gather reads neighbours)");
+    const struct { const void* p; uint64_t bytes; const char* name; } outs[3] = {{film_out, film_bytes, "film_out"}, {variance_out, plane_bytes, "variance_out"},
+                                                                                  {history_out, history_bytes, "history_out"}},
+        ins[5] = {{film_accum, film_bytes, "film_accum"}, {variance, plane_bytes, "variance"}, {normal_accum, film_bytes, "normal_accum"},
+                  {depth_accum, film_bytes, "depth_accum"}, {history_in, history_bytes, "history_in"}};
+    for (int o = 0; o < 3; ++o) {
+        for (const auto& in : ins)
+            if (overlaps(outs[o].p, outs[o].bytes, in.p, in.bytes))
+                return fail(ctx, GBL_ERR_INVALID, std::string("gbl_film_accumulate: ") + outs[o].name + " may not overlap " + in.name);
+        for (int q = o + 1; q < 3; ++q)
+            if (overlaps(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes))
+                return fail(ctx, GBL_ERR_INVALID, std::string("gbl_film_accumulate: ") + outs[o].name + " may not overlap " + outs[q].name);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    gbl_status st;
+    if ((st = grow(ctx, ctx->temporal, 2 * film_bytes + plane_bytes, "temporal planes")) != GBL_OK) return st;
+    float4* const cl = static_cast<float4*>(ctx->temporal.p);
+    float4* const nz = cl + n;
+    uint32_t* const fl = reinterpret_cast<uint32_t*>(nz + n);
+    gbl_launch_temporal_prepare(film_accum, variance, normal_accum, depth_accum, cl, nz, fl, n, stream);
+    HIP_TRY(ctx, hipGetLastError());
+    TemporalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.W = width;
+    a.H = height;
+    a.cur = ctx->scene.camera;
+    if (history_in) pack_camera(p->prev_camera, ctx->h_film, &a.prev);
+    a.alpha_min = p->alpha_min;
+    a.max_history = p->max_history;
+    a.sigma_depth = p->sigma_depth;
+    a.cos_normal = p->cos_normal;
+    a.has_normal = normal_accum ? 1u : 0u;
+    a.has_history = history_in ? 1u : 0u;
+    gbl_launch_temporal_accumulate(!variance, cl, nz, fl, variance, history_in, history_out, film_out, variance_out, a, stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+gbl_status gbl_film_accumulate(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* normal_accum, const float* depth_accum,
+                               const float* history_in, float* history_out, const gbl_temporal_params* params, float* film_out, float* variance_out) {
+    return gbl_guard([&] { return gbl_film_accumulate_impl(ctx, film_accum, variance, normal_accum, depth_accum, history_in, history_out, params, film_out,
+                                                           variance_out); },
                      [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 

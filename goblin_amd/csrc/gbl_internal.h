@@ -15,6 +15,7 @@
 #include "kernels/wf_args.h"
 #include "kernels/aov_args.h"
 #include "kernels/denoise_args.h"
+#include "kernels/temporal_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -60,8 +61,13 @@ struct gbl_ctx {
     int dev_filter_fw = 0;    // ... and the filter width it was built for (0: none yet)
     gbl_buf denoise;          // gbl_film_denoise's four float4 planes (kernels/denoise.h): cv ping, cv pong, nz, af
     bool denoise_lds_allowed = false;   // ... its staging level kernel may be launched with more than 64 KB of LDS on this device
+    gbl_buf temporal;         // gbl_film_accumulate's prepared frame (kernels/temporal.h): cl, nz (float4 each) and the flags
     std::map<int, float> auto_rays_per_path;   // GBL_SCHEDULE_AUTO's pilot: rays per camera path by 2 * max_ray_depth + russian_roulette (gbl_render)
     double build_ms = 0.0;    // pack_scene + BVH construction + node / triangle upload
+    // what gbl_update_camera and gbl_film_accumulate need to pack a camera (scene_prep.h pack_camera)
+    gbl_camera h_camera;      // the description last set: gbl_create's at first (gbl_get_camera)
+    gbl_film h_film;
+    int32_t scene_extended = 0;   // DevScene::extended without the camera's part
     // what gbl_update_instances needs to rebuild the TLAS
     std::vector<gbl_instance> h_instances;
     std::vector<uint32_t> h_light_slots;   // DevLight::wh_n per light (the Whitted quota, host copy for the stream sampler's layout)
@@ -143,6 +149,11 @@ size_t gbl_denoise_lds_bytes(int stride);   // of the staging level kernel; 0 wh
 hipError_t gbl_launch_denoise_level(bool lds, const float4* cv_in, const float4* nz, const float4* af, float4* cv_out, const DenoiseArgs& a, hipStream_t stream,
                                     bool* lds_allowed);
 void gbl_launch_denoise_finish(const float4* cv, const float4* af, float* film_out, int n, uint32_t demodulate, hipStream_t stream);
+// kernels_temporal.hip: the passes of gbl_film_accumulate (kernels/temporal.h)
+void gbl_launch_temporal_prepare(const float* film, const float* variance, const float* normal, const float* depth, float4* cl, float4* nz, uint32_t* fl,
+                                 int n, hipStream_t stream);
+void gbl_launch_temporal_accumulate(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance, const float* history_in,
+                                    float* history_out, float* film_out, float* variance_out, const TemporalArgs& a, hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

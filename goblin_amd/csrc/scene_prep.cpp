@@ -649,12 +649,32 @@ void reference_order(const float* P, const uint32_t* I, uint32_t n, DevTriOrder*
 }
 }   // namespace
 
+bool camera_extended(const gbl_camera& c) { return c.lens_radius != 0.0f || c.type != GBL_CAMERA_PERSPECTIVE; }
+
+void pack_camera(const gbl_camera& c, const gbl_film& film, DevCamera* out) {
+    memset(out, 0, sizeof(*out));
+    for (int k = 0; k < 3; ++k) out->pos[k] = c.position[k];
+    for (int k = 0; k < 4; ++k) out->q[k] = c.orientation[k];
+    float aspect = static_cast<float>(film.xres) / static_cast<float>(film.yres);
+    float fov = kPi * (c.fov_degrees / 180.0f);
+    float ys = 1.0f / std::tan(fov / 2.0f);
+    out->proj11 = ys;
+    out->proj00 = ys / aspect;
+    out->inv_xres = 1.0f / static_cast<float>(film.xres);
+    out->inv_yres = 1.0f / static_cast<float>(film.yres);
+    out->type = c.type;
+    out->lens_radius = c.lens_radius;
+    out->focal_distance = c.focal_distance;
+    out->film_w = c.film_width;              // OrthographicCamera ctor, GoblinCamera.cpp:288-296
+    out->film_h = c.film_width / aspect;
+}
+
 gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* err, bool device_blas) {
     if (!d || d->abi_version != GBL_ABI_VERSION) {
         *err = "scene description has the wrong abi_version";
         return GBL_ERR_INVALID;
     }
-    out->extended = (d->camera.lens_radius != 0.0f || d->camera.type != GBL_CAMERA_PERSPECTIVE) ? 1 : 0;
+    out->extended = 0;   // the scene's part first; the camera's is added where the camera is packed
     if (d->camera.type > GBL_CAMERA_ORTHOGRAPHIC) {
         *err = "unknown camera type";
         return GBL_ERR_INVALID;
@@ -1310,22 +1330,9 @@ gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* er
     }
 
     // ---- camera
-    const gbl_camera& c = d->camera;
-    memset(&out->camera, 0, sizeof(out->camera));
-    for (int k = 0; k < 3; ++k) out->camera.pos[k] = c.position[k];
-    for (int k = 0; k < 4; ++k) out->camera.q[k] = c.orientation[k];
-    float aspect = static_cast<float>(d->film.xres) / static_cast<float>(d->film.yres);
-    float fov = kPi * (c.fov_degrees / 180.0f);
-    float ys = 1.0f / std::tan(fov / 2.0f);
-    out->camera.proj11 = ys;
-    out->camera.proj00 = ys / aspect;
-    out->camera.inv_xres = 1.0f / static_cast<float>(d->film.xres);
-    out->camera.inv_yres = 1.0f / static_cast<float>(d->film.yres);
-    out->camera.type = c.type;
-    out->camera.lens_radius = c.lens_radius;
-    out->camera.focal_distance = c.focal_distance;
-    out->camera.film_w = c.film_width;              // OrthographicCamera ctor, GoblinCamera.cpp:288-296
-    out->camera.film_h = c.film_width / aspect;
+    out->scene_extended = out->extended;
+    if (camera_extended(d->camera)) out->extended = 1;
+    pack_camera(d->camera, d->film, &out->camera);
 
     // ---- film + filter table
     const gbl_film& f = d->film;

@@ -29,6 +29,7 @@ struct PackedScene {
     int32_t tlas_root = 0;
     int32_t stack_entries = 0;
     int32_t extended = 0;   // DevScene::extended
+    int32_t scene_extended = 0;   // ... without the camera's part (camera_extended)
     int32_t has_masks = 0;  // DevScene::has_masks
     int32_t has_bssrdf = 0; // DevScene::has_bssrdf
     int32_t wh_slots = 0;   // DevScene::wh_slots
@@ -50,6 +51,12 @@ struct PackedScene {
 // (at indices 0..), `tris` stays empty, mesh instances get root = 0 (patched after the device build) and
 // `mesh_lo/hi` carry the object bounds the Morton codes are scaled by.
 gbl_status pack_scene(const gbl_scene_desc* desc, PackedScene* out, std::string* err, bool device_blas = false);
+
+// The device camera of a description under a film's resolution: what gbl_create, gbl_update_camera and gbl_film_accumulate (for
+// its previous camera) share.  The type is the caller's to check.
+void pack_camera(const gbl_camera& camera, const gbl_film& film, DevCamera* out);
+// The camera's part of DevScene::extended: a thin lens or an orthographic camera needs the EXT kernels
+bool camera_extended(const gbl_camera& camera);
 
 // The instance records and the TLAS over them (also used by gbl_update_instances to rebuild after transform edits).
 gbl_status build_tlas(const gbl_instance* inst, uint32_t n, const gbl_mesh* meshes, const gbl_material* materials, const float* mesh_lo,

@@ -81,6 +81,32 @@ class HipPathTracer:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         self.lib.gbl_get_info(self.handle, C.byref(self.info))
 
+    def camera(self):
+        """The camera description last set (gbl_get_camera): a gbl_camera, the scene's at first."""
+        cam = _abi.gbl_camera()
+        st = self.lib.gbl_get_camera(self.handle, C.byref(cam))
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return cam
+
+    def update_camera(self, position=None, orientation=None, **fields):
+        """Give the context a new camera (gbl_update_camera): position (3), orientation (w, x, y, z) and any other gbl_camera
+        field by name (fov_degrees, lens_radius, focal_distance, type, film_width, ...); what is not given keeps its value.
+        Host work only: nothing is rebuilt or uploaded, and renders already queued keep the camera they were launched with."""
+        cam = self.camera()
+        if position is not None:
+            cam.position[:] = [float(v) for v in position]
+        if orientation is not None:
+            cam.orientation[:] = [float(v) for v in orientation]
+        names = {name for name, _ in _abi.gbl_camera._fields_} - {"position", "orientation"}
+        for name, value in fields.items():
+            if name not in names:
+                raise TypeError("gbl_camera has no field %r" % name)
+            setattr(cam, name, value)
+        st = self.lib.gbl_update_camera(self.handle, C.byref(cam))
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
         if h:
@@ -306,3 +332,53 @@ class HipPathTracer:
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return out
+
+    def new_history(self):
+        """A history for ``accumulate``: (3, yres, xres, 4) float32 zeros on the device -- the planes {c.rgb, N}, {m1, m2, v, z} and
+        {n.xyz, surf}.  N = 0 everywhere: no pixel has history yet."""
+        torch = _torch()
+        return torch.zeros((3, self.info.yres, self.info.xres, 4), dtype=torch.float32, device=self.device)
+
+    def accumulate(self, film, depth, variance=None, normal=None, history=None, prev_camera=None, alpha_min=0.1, max_history=64.0,
+                   sigma_depth=0.05, cos_normal=0.9):
+        """Reprojected temporal accumulation (gbl_film_accumulate) on the current stream: blends the frame ``film`` (rendered
+        under the tracer's current camera) into ``history``, the "history" a previous call returned, fetched from where each
+        pixel's surface lay under ``prev_camera`` (a gbl_camera: ``camera()`` as it was when that frame was rendered).
+        ``depth`` and ``normal`` are render_aov's films, ``variance`` the plane of ``variance()``; without it the variance is
+        estimated from the accumulated luminance moments and the current frame's neighbourhood.  history=None starts a
+        sequence.  Returns {"film": Film {rgb, 1} (``denoise``, ``normalized`` and ``develop`` take it as a rendered one),
+        "variance": (yres, xres) variance of the accumulated pixel, "history": the new history (the input one is not touched)}."""
+        torch = _torch()
+        h, w = self.info.yres, self.info.xres
+
+        def plane(t, shape, what):
+            if t is None:
+                return None
+            t = t.accum if isinstance(t, Film) else t
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s float32 tensor on %s" % (what, shape, self.device))
+            return t
+        accum, dep = plane(film, (h, w, 4), "film"), plane(depth, (h, w, 4), "depth")
+        if accum is None or dep is None:
+            raise ValueError("accumulate needs a film and a depth film")
+        var, nrm = plane(variance, (h, w), "variance"), plane(normal, (h, w, 4), "normal")
+        hist = plane(history, (3, h, w, 4), "history")
+        if hist is not None and prev_camera is None:
+            raise ValueError("a history needs the camera it was accumulated under (prev_camera)")
+        p = _abi.gbl_temporal_params()
+        if prev_camera is not None:
+            p.prev_camera = prev_camera
+        p.alpha_min, p.max_history = float(alpha_min), float(max_history)
+        p.sigma_depth, p.cos_normal = float(sigma_depth), float(cos_normal)
+        p.stream = torch.cuda.current_stream(self.device).cuda_stream
+        out = Film(w, h, self.device)
+        var_out = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        hist_out = torch.empty((3, h, w, 4), dtype=torch.float32, device=self.device)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        st = self.lib.gbl_film_accumulate(self.handle, accum.data_ptr(), ptr(var), ptr(nrm), dep.data_ptr(), ptr(hist), hist_out.data_ptr(),
+                                          C.byref(p), out.accum.data_ptr(), var_out.data_ptr())
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return {"film": out, "variance": var_out, "history": hist_out}

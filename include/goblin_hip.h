@@ -582,6 +582,38 @@ gbl_status gbl_film_denoise(gbl_ctx* ctx, const float* film_accum, const float* 
                             const float* albedo_accum, const float* normal_accum, const float* depth_accum /* each or NULL */,
                             const gbl_denoise_params* params, float* film_out /* xres*yres float4 */);
 
+/* Reprojected temporal accumulation of a film (DESIGN.md 4.7 states it operation by operation): the frame just rendered is
+ * blended into a history fetched from where each pixel's surface point lay under the previous camera, with a history length per
+ * pixel.  The current camera is the context's (gbl_update_camera); the history is the caller's, so a context holds no frame
+ * state and a caller may keep several.  A history is three planes of xres*yres float4 in device memory, one after the other:
+ * H0 = {c.rgb, N}, H1 = {m1, m2, v, z}, H2 = {n.xyz, surf ? 1 : 0} -- accumulated colour and history length, the first two
+ * moments of the luminance, the variance of the accumulated pixel, and the depth and normal the next frame tests its taps
+ * against.  history_in = NULL starts a sequence (N = 1 everywhere).  history_out may not overlap history_in: the gather reads
+ * neighbours.  film_out: {rgb, 1} for a valid pixel, zeros (in every output, so N = 0) for one of weight 0 or with a non-finite
+ * input; it takes the denoiser's place in the chain, and gbl_film_denoise(film_out, variance_out, albedo, normal, depth),
+ * gbl_film_resolve and gbl_film_develop accept it unchanged.  variance_out is the variance of the accumulated pixel: blended
+ * from `variance` where that plane is given, otherwise estimated from the accumulated luminance moments (N >= 4) or from the
+ * 5 x 5 neighbourhood of the current frame -- a variance for films that arrive without per-sample radiance.  Limits: a thin
+ * lens is reprojected as its pinhole; pixels without coverage (the background) do not accumulate; moving instances are not
+ * reprojected, a moved instance ghosts until the depth or normal test rejects it.  No output may overlap an input or another
+ * output.  Asynchronous on params->stream; the scratch lives in the context: calls that share a context are ordered by the
+ * caller. */
+#define GBL_HISTORY_FLOATS_PER_PIXEL 12   /* three float4 planes of xres*yres, caller-owned, device memory */
+typedef struct gbl_temporal_params {
+    gbl_camera prev_camera;  /* the camera history_in was accumulated under; ignored when history_in is NULL */
+    float alpha_min;         /* in (0, 1]: floor of the blend weight */
+    float max_history;       /* >= 1: the history length is clamped to it */
+    float sigma_depth;       /* > 0: relative depth tolerance of a history tap and of the spatial estimate */
+    float cos_normal;        /* in [-1, 1]: smallest n_prev . n_cur of an accepted tap; read only with a normal film */
+    uint32_t reserved;
+    void* stream;            /* hipStream_t, NULL = default stream */
+} gbl_temporal_params;
+gbl_status gbl_film_accumulate(gbl_ctx* ctx, const float* film_accum, const float* variance /* or NULL */,
+                               const float* normal_accum /* or NULL */, const float* depth_accum,
+                               const float* history_in /* or NULL: first frame */, float* history_out,
+                               const gbl_temporal_params* params, float* film_out /* float4, {rgb, 1} */,
+                               float* variance_out /* xres*yres, or NULL */);
+
 /* Device time of recent gbl_render calls, from HIP events recorded on the render stream
  * around the dominant kernel and around the whole call (no host synchronisation happens
  * inside gbl_render for this).  out[0] is the most recent call.  Blocks until those events
@@ -614,6 +646,16 @@ gbl_status gbl_get_info(const gbl_ctx* ctx, gbl_info* out);
  * the device.  Instances that carry an area light, and scenes with a directional or image based light (whose power and
  * sampling sphere depend on the scene bound), are GBL_ERR_UNSUPPORTED: re-create the context for those. */
 gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world);
+
+/* Camera edit: every later call on the context sees `camera`; film and resolution stay the context's.  Host work only (the
+ * scene is neither rebuilt nor uploaded) and no device synchronisation: every kernel receives the camera by value, so work
+ * already queued keeps the old one.  A thin lens or an orthographic camera switches the calls to the kernels that know them,
+ * a pinhole back to the lean ones; the lens disk a scene file adds beside a thin lens is an instance and stays the scene's.
+ * GBL_SCHEDULE_AUTO measures its rays per path again.  GBL_ERR_INVALID, the context unchanged, for a NULL argument, a type
+ * beyond GBL_CAMERA_ORTHOGRAPHIC and a non-finite position, orientation or fov_degrees.  gbl_get_camera returns the
+ * description last set, gbl_create's at first. */
+gbl_status gbl_update_camera(gbl_ctx* ctx, const gbl_camera* camera);
+gbl_status gbl_get_camera(const gbl_ctx* ctx, gbl_camera* out);
 
 /* Self-test hook: the device's sinf / cosf (glibc's algorithm restated, kernels/refmath.h) on n device floats. */
 gbl_status gbl_selftest_sincos(gbl_ctx* ctx, const float* in, float* sin_out, float* cos_out, uint64_t n);
