@@ -27,6 +27,17 @@ OBJ = os.path.join(LIB, "obj")
 # CPU build; the BVH slab tests opt back in with explicit __builtin_fmaf.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
              "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-munsafe-fp-atomics"]
+# Flags of single kernel units, after HIP_FLAGS (basename without ".hip").  -fno-slp-vectorize: in the traversal kernels the
+# SLP vectoriser's v_pk_mul_f32 / v_pk_add_f32 pairs cost more register moves than they save issue slots and push the lean quad
+# kernels into VGPR spills (profiles/slp_splat_ab.txt has the A/B per unit).  The values do not change:
+# only IEEE mul / add and the explicit __builtin_fmaf get paired.
+_NO_SLP = ["-fno-slp-vectorize"]
+UNIT_FLAGS = {"kernels_quad": _NO_SLP, "kernels_path": _NO_SLP, "kernels_wavefront": _NO_SLP, "kernels_stream": _NO_SLP,
+              "kernels_whitted": _NO_SLP, "kernels_aux": _NO_SLP, "kernels_aov": _NO_SLP}
+
+
+def unit_flags(src_or_unit):
+    return list(UNIT_FLAGS.get(os.path.splitext(os.path.basename(src_or_unit))[0], ()))
 
 
 def _stale(target, deps):
@@ -61,14 +72,23 @@ def build_host(force=False):
     return out
 
 
+def _compile(src, obj, flags, force):
+    """One object; rebuilt when a prerequisite of its depfile is newer or its flags are not the ones it was built with."""
+    dep, rec = obj + ".d", obj + ".flags"
+    deps = _depfile_deps(dep)
+    line = " ".join(flags)
+    same = os.path.exists(rec) and open(rec).read() == line
+    if force or deps is None or not same or _stale(obj, [src] + deps):
+        _run([HIPCC] + flags + ["-c", src, "-o", obj, "-MD", "-MF", dep])
+        with open(rec, "w") as f:
+            f.write(line)
+        return True
+    return False
+
+
 def _hip_object(src, force, extra_flags):
     obj = os.path.join(OBJ, os.path.splitext(os.path.basename(src))[0] + ".o")
-    dep = obj + ".d"
-    deps = _depfile_deps(dep)
-    if force or deps is None or _stale(obj, [src] + deps):
-        _run([HIPCC] + HIP_FLAGS + list(extra_flags) + ["-c", src, "-o", obj, "-MD", "-MF", dep])
-        return obj, True
-    return obj, False
+    return obj, _compile(src, obj, HIP_FLAGS + unit_flags(src) + list(extra_flags), force)
 
 
 def build_hip(force=False, extra_flags=(), jobs=None):
@@ -114,10 +134,7 @@ def build_tie_inline(force=False):
     def one(unit):
         src = os.path.join(CSRC, unit + ".hip")
         obj = os.path.join(odir, unit + ".o")
-        dep = obj + ".d"
-        deps = _depfile_deps(dep)
-        if force or deps is None or _stale(obj, [src] + deps):
-            _run([HIPCC] + HIP_FLAGS + ["-DGBL_TIE_INLINE", "-c", src, "-o", obj, "-MD", "-MF", dep])
+        _compile(src, obj, HIP_FLAGS + unit_flags(unit) + ["-DGBL_TIE_INLINE"], force)
         return obj
     with ThreadPoolExecutor(max_workers=len(TIE_INLINE_UNITS)) as pool:
         vobjs = list(pool.map(one, TIE_INLINE_UNITS))
@@ -163,9 +180,11 @@ def _code_only(text):
 def source_stamp():
     """sha256 (first 16 hex digits) over the CODE of every source file the HIP library is built from -- comments and white
     space do not count, so a note added beside a kernel does not orphan the counters collected from it: profiles/ records
-    the stamp with the counters it collects, bench.py only quotes counters whose stamp is the running tree's."""
+    the stamp with the counters it collects, bench.py only quotes counters whose stamp is the running tree's.  The compiler
+    flags count too: HIP_FLAGS and the per-unit table make a different binary of the same sources."""
     import hashlib
     h = hashlib.sha256()
+    h.update(repr((HIP_FLAGS, sorted((u, list(f)) for u, f in UNIT_FLAGS.items()))).encode())
     files = []
     for root, _, names in os.walk(CSRC):
         files += [os.path.join(root, n) for n in names if n.endswith((".h", ".hip", ".cpp"))]

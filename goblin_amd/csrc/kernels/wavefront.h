@@ -664,6 +664,108 @@ __device__ __forceinline__ float4 wf_apply_medium(const RenderArgs& ra, float4 L
 }
 
 // ---------------------------------------------------------------------------
+// The fast path of wf_splat: every sample of pixel (px, py) lies inside its pixel and the filter's half-widths are <= 2, so
+// its footprint is inside the 5x5 block around the pixel -- the lane accumulates its samples in registers and touches the
+// LDS tile once per footprint cell.  What the call or the pixel decides is taken out of the loop over the samples:
+//   * POW2 (both half-widths powers of two, every default filter): the bin min(int(floorf(fabsf(16 (x - dx) / w))), 15) takes
+//     (16 (x - dx)) * (1 / w), the same float for every input (scaling by a power of two is exact both ways), instead of one
+//     of ten IEEE divisions per sample (110 instructions); any other width keeps the division;
+//   * the film's crop bounds and float(x) of the five columns and rows are the pixel's, taken once; a row's table offset once
+//     per row, and its five weights read in one LDS round trip ahead of the cells' branches.
+// The sums take the same addends in the same order as ImageTile::addSample's cells did before: same samples per (wave, lane),
+// same 25-cell order, same atomics.  Measured and not kept (DESIGN_HISTORY, "SLP pairing off ..."): the 25 cells as straight-line
+// code with a select on each sum, and the radiance staged through LDS with coalesced loads.
+template <bool REPLAY, bool STATS, bool POW2>
+__device__ __forceinline__ void wf_splat_fast5(const DevScene& sc, const RenderArgs& ra, const WfArgs& wa, const float* ftab, float* tile, int tp,
+                                               int tx0, int ty0, int px, int py, LaneCounters& cnt) {
+    const int wave = threadIdx.x >> 6;
+    SampleSource src = camera_source<false>(sc, ra, px, py, 0u, nullptr);   // (the native law's; src.k per sample)
+    const uint32_t local_pixel = window_pixel(ra, px, py);
+    float acc[25][4];
+#pragma unroll
+    for (int i = 0; i < 25; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0f;
+    const float wx = sc.film.wx, wy = sc.film.wy;
+    const float rx = POW2 ? 1.0f / wx : wx, ry = POW2 ? 1.0f / wy : wy;
+    const int xlo = sc.film.xstart, xhi = sc.film.xstart + sc.film.xcount - 1;
+    const int ylo = sc.film.ystart, yhi = sc.film.ystart + sc.film.ycount - 1;
+    float fx[5], fy[5];
+    bool inx[5], iny[5];
+#pragma unroll
+    for (int o = 0; o < 5; ++o) {
+        const int x = px + o - 2, y = py + o - 2;
+        fx[o] = static_cast<float>(x);
+        fy[o] = static_cast<float>(y);
+        inx[o] = x >= xlo && x <= xhi;
+        iny[o] = y >= ylo && y <= yhi;
+    }
+    for (int kk = wave; kk < wa.pass_spp; kk += GBL_BLOCK / 64) {
+        src.k = static_cast<uint32_t>(wa.pass_k0 + kk);
+        float image_x, image_y;
+        if (REPLAY) {
+            const float* xy = ra.image_xy + 2 * (static_cast<size_t>(local_pixel) * ra.spp + src.k);
+            image_x = xy[0];
+            image_y = xy[1];
+        } else {
+            image_position<false>(src, px, py, &image_x, &image_y);
+        }
+        const float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
+                                         static_cast<size_t>(local_pixel) * ra.spp + src.k);
+        if (L.x != L.x || L.y != L.y || L.z != L.z) continue;   // NaN sample: dropped
+        const float dx = image_x - 0.5f, dy = image_y - 0.5f;
+        const int cx0 = static_cast<int>(ceilf(dx - wx)), cx1 = static_cast<int>(floorf(dx + wx));
+        const int cy0 = static_cast<int>(ceilf(dy - wy)), cy1 = static_cast<int>(floorf(dy + wy));
+        int ix[5], row[5];
+        bool onx[5], ony[5];
+#pragma unroll
+        for (int o = 0; o < 5; ++o) {
+            const int x = px + o - 2, y = py + o - 2;
+            const float tx = 16 * (fx[o] - dx), ty = 16 * (fy[o] - dy);
+            ix[o] = min(static_cast<int>(floorf(fabsf(POW2 ? tx * rx : tx / rx))), 15);
+            row[o] = 16 * min(static_cast<int>(floorf(fabsf(POW2 ? ty * ry : ty / ry))), 15);
+            onx[o] = inx[o] && x >= cx0 && x <= cx1;
+            ony[o] = iny[o] && y >= cy0 && y <= cy1;
+        }
+#pragma unroll
+        for (int oy = 0; oy < 5; ++oy) {
+            // a row's five weights are read together, ahead of the cells' branches (a bin is a valid index whether or not its
+            // cell is in the footprint): one LDS round trip per row, not one per cell behind its branch
+            float w[5];
+#pragma unroll
+            for (int ox = 0; ox < 5; ++ox) w[ox] = ftab[row[oy] + ix[ox]];
+#pragma unroll
+            for (int ox = 0; ox < 5; ++ox) {
+                if (onx[ox] && ony[oy]) {
+                    float* a = acc[oy * 5 + ox];
+                    a[0] += w[ox] * L.x;
+                    a[1] += w[ox] * L.y;
+                    a[2] += w[ox] * L.z;
+                    a[3] += w[ox];
+                    if (STATS) cnt.splats += 1;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int oy = 0; oy < 5; ++oy) {
+#pragma unroll
+        for (int ox = 0; ox < 5; ++ox) {
+            const float* a = acc[oy * 5 + ox];
+            if (a[3] != 0.0f || a[0] != 0.0f || a[1] != 0.0f || a[2] != 0.0f) {
+                float* q = tile + 4 * ((py + oy - 2 - ty0) * tp + (px + ox - 2 - tx0));
+                atomicAdd(q + 0, a[0]);
+                atomicAdd(q + 1, a[1]);
+                atomicAdd(q + 2, a[2]);
+                atomicAdd(q + 3, a[3]);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ bool wf_power_of_two(float w) {   // a normal float with an empty mantissa
+    const uint32_t u = __float_as_uint(w);
+    return (u & 0x807fffffu) == 0u && (u >> 23) != 0u && (u >> 23) != 255u;
+}
+
 template <bool REPLAY, bool STATS>
 __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra, WfArgs wa) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -687,84 +789,30 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra
     // (The stream sampler's records are the reference's own: also inside their pixel; their image positions were kept
     // in ra.image_xy.  Arbitrary replay records may belong anywhere and take the general path.)
     const bool fast5 = (!REPLAY || ra.image_xy != nullptr) && sc.film.wx <= 2.0f && sc.film.wy <= 2.0f;
-    if (px < ra.window[1] && py < ra.window[3]) {
+    const bool valid = px < ra.window[1] && py < ra.window[3];
+    if (valid && fast5) {
+        if (wf_power_of_two(sc.film.wx) && wf_power_of_two(sc.film.wy))   // (uniform over the launch)
+            wf_splat_fast5<REPLAY, STATS, true>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+        else
+            wf_splat_fast5<REPLAY, STATS, false>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+    } else if (valid) {
         SampleSource src = camera_source<false>(sc, ra, px, py, 0u, nullptr);   // (the native law's; src.k and src.rec per sample)
         const uint32_t local_pixel = window_pixel(ra, px, py);
-        if (fast5) {
-            float acc[25][4];
-#pragma unroll
-            for (int i = 0; i < 25; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0f;
-            const int xlo = sc.film.xstart, xhi = sc.film.xstart + sc.film.xcount - 1;
-            const int ylo = sc.film.ystart, yhi = sc.film.ystart + sc.film.ycount - 1;
-            for (int kk = wave; kk < wa.pass_spp; kk += GBL_BLOCK / 64) {
-                src.k = static_cast<uint32_t>(wa.pass_k0 + kk);
-                float image_x, image_y;
-                if (REPLAY) {
-                    const float* xy = ra.image_xy + 2 * (static_cast<size_t>(local_pixel) * ra.spp + src.k);
-                    image_x = xy[0];
-                    image_y = xy[1];
-                } else {
-                    image_position<false>(src, px, py, &image_x, &image_y);
-                }
-                const float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
-                                                 static_cast<size_t>(local_pixel) * ra.spp + src.k);
-                if (L.x != L.x || L.y != L.y || L.z != L.z) continue;   // NaN sample: dropped
-                const float dx = image_x - 0.5f, dy = image_y - 0.5f;
-                const int x0 = max(static_cast<int>(ceilf(dx - sc.film.wx)), xlo), x1 = min(static_cast<int>(floorf(dx + sc.film.wx)), xhi);
-                const int y0 = max(static_cast<int>(ceilf(dy - sc.film.wy)), ylo), y1 = min(static_cast<int>(floorf(dy + sc.film.wy)), yhi);
-                int ix[5], iy[5];
-#pragma unroll
-                for (int o = 0; o < 5; ++o) {
-                    const int x = px + o - 2, y = py + o - 2;
-                    ix[o] = (x >= x0 && x <= x1) ? min(static_cast<int>(floorf(fabsf(16 * (x - dx) / sc.film.wx))), 15) : -1;
-                    iy[o] = (y >= y0 && y <= y1) ? min(static_cast<int>(floorf(fabsf(16 * (y - dy) / sc.film.wy))), 15) : -1;
-                }
-#pragma unroll
-                for (int oy = 0; oy < 5; ++oy) {
-#pragma unroll
-                    for (int ox = 0; ox < 5; ++ox) {
-                        if (ix[ox] >= 0 && iy[oy] >= 0) {
-                            const float w = ftab[iy[oy] * 16 + ix[ox]];
-                            acc[oy * 5 + ox][0] += w * L.x;
-                            acc[oy * 5 + ox][1] += w * L.y;
-                            acc[oy * 5 + ox][2] += w * L.z;
-                            acc[oy * 5 + ox][3] += w;
-                            if (STATS) cnt.splats += 1;
-                        }
-                    }
-                }
+        for (int kk = wave; kk < wa.pass_spp; kk += GBL_BLOCK / 64) {
+            const uint32_t k = static_cast<uint32_t>(wa.pass_k0 + kk);
+            float image_x, image_y;
+            if (REPLAY && ra.image_xy) {   // GBL_SAMPLES_STREAM: the records were transient, their image positions were kept
+                const float* xy = ra.image_xy + 2 * (static_cast<size_t>(local_pixel) * ra.spp + k);
+                image_x = xy[0];
+                image_y = xy[1];
+            } else {
+                src.k = k;
+                if (REPLAY) src.rec = ra.replay + (static_cast<size_t>(local_pixel) * ra.spp + k) * ra.dims;
+                image_position<REPLAY>(src, px, py, &image_x, &image_y);
             }
-#pragma unroll
-            for (int oy = 0; oy < 5; ++oy) {
-#pragma unroll
-                for (int ox = 0; ox < 5; ++ox) {
-                    const float* a = acc[oy * 5 + ox];
-                    if (a[3] != 0.0f || a[0] != 0.0f || a[1] != 0.0f || a[2] != 0.0f) {
-                        float* q = tile + 4 * ((py + oy - 2 - ty0) * tp + (px + ox - 2 - tx0));
-                        atomicAdd(q + 0, a[0]);
-                        atomicAdd(q + 1, a[1]);
-                        atomicAdd(q + 2, a[2]);
-                        atomicAdd(q + 3, a[3]);
-                    }
-                }
-            }
-        } else {
-            for (int kk = wave; kk < wa.pass_spp; kk += GBL_BLOCK / 64) {
-                const uint32_t k = static_cast<uint32_t>(wa.pass_k0 + kk);
-                float image_x, image_y;
-                if (REPLAY && ra.image_xy) {   // GBL_SAMPLES_STREAM: the records were transient, their image positions were kept
-                    const float* xy = ra.image_xy + 2 * (static_cast<size_t>(local_pixel) * ra.spp + k);
-                    image_x = xy[0];
-                    image_y = xy[1];
-                } else {
-                    src.k = k;
-                    if (REPLAY) src.rec = ra.replay + (static_cast<size_t>(local_pixel) * ra.spp + k) * ra.dims;
-                    image_position<REPLAY>(src, px, py, &image_x, &image_y);
-                }
-                float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
-                                           static_cast<size_t>(local_pixel) * ra.spp + k);
-                splat<STATS>(sc.film, ftab, tile, tx0, ty0, tp, image_x, image_y, f3(L.x, L.y, L.z), cnt);
-            }
+            float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
+                                       static_cast<size_t>(local_pixel) * ra.spp + k);
+            splat<STATS>(sc.film, ftab, tile, tx0, ty0, tp, image_x, image_y, f3(L.x, L.y, L.z), cnt);
         }
     }
     __syncthreads();
