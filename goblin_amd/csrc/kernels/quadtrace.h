@@ -205,22 +205,26 @@ __device__ __forceinline__ void quad_transition(const DevScene& sc, TravState& s
     if (STATS) probe(cnt.oth_lane, cnt.oth_wave);
     const F3 wo = f3(__uint_as_float(rec[6]), __uint_as_float(rec[7]), __uint_as_float(rec[8]));
     const F3 wd = f3(__uint_as_float(rec[9]), __uint_as_float(rec[10]), __uint_as_float(rec[11]));
+    // one ray_space() for both directions: the world ray itself when the ray leaves an instance, its image under the instance's
+    // inverse transform when it enters one -- the operands, and so the values, of a call per direction, and one definition of st.r
+    F3 so = wo, sd = wd;
     if (st.cur == GBL_STACK_SENTINEL) {   // finished an instance: back to the world ray
-        ray_space(st.r, wo, wd);
         st.inst = -1;
         st.cur = static_cast<int>(stk.load(--st.sp));
-        return;
+    } else {
+        const uint32_t ref = ~static_cast<uint32_t>(st.cur);
+        const DevInstance* ip = sc.instances + (ref >> 2);
+        if (EXT && filter != GBL_FILTER_NONE && (ip->is_mask != 0u ? GBL_FILTER_MASK : GBL_FILTER_OPAQUE) != filter) {
+            st.cur = static_cast<int>(stk.load(--st.sp));
+            return;
+        }
+        st.inst = static_cast<int>(ref >> 2);
+        so = xf_point(ip->inv, wo);
+        sd = xf_vector(ip->inv, wd);
+        stk.store(st.sp++, GBL_STACK_SENTINEL);
+        st.cur = ip->root;
     }
-    const uint32_t ref = ~static_cast<uint32_t>(st.cur);
-    const DevInstance* ip = sc.instances + (ref >> 2);
-    if (EXT && filter != GBL_FILTER_NONE && (ip->is_mask != 0u ? GBL_FILTER_MASK : GBL_FILTER_OPAQUE) != filter) {
-        st.cur = static_cast<int>(stk.load(--st.sp));
-        return;
-    }
-    st.inst = static_cast<int>(ref >> 2);
-    ray_space(st.r, xf_point(ip->inv, wo), xf_vector(ip->inv, wd));
-    stk.store(st.sp++, GBL_STACK_SENTINEL);
-    st.cur = ip->root;
+    ray_space(st.r, so, sd);
 }
 
 // trace() for a whole wave: every lane of the wave calls it (`want`: the lane has a ray); the exits are wave-uniform.
@@ -284,7 +288,7 @@ __device__ __forceinline__ bool trace_quad(const DevScene& sc, bool want, F3 o, 
                 }
                 if (!at_int) {
                     const unsigned long long b0 = __builtin_amdgcn_s_memtime();
-                    done = trav_other<ANY, STATS, EXT, LdsStack, TM, false>(sc, st, stk, cnt, &occluded, filter);
+                    done = trav_other<ANY, STATS, EXT, LdsStack, TM, GBL_FUSE_NONE>(sc, st, stk, cnt, &occluded, filter);
                     asm volatile("" ::"v"(st.cur), "v"(st.sp));
                     cnt.pc[12] += __builtin_amdgcn_s_memtime() - b0;
                     cnt.pc[14] += 1;
@@ -300,10 +304,10 @@ __device__ __forceinline__ bool trace_quad(const DevScene& sc, bool want, F3 o, 
                     trav_interior<STATS, !ANY>(sc, st, stk, cnt);
                     if (STATS) ++steps;
                 } else {
-                    done = trav_other<ANY, STATS, EXT, LdsStack, TM, false>(sc, st, stk, cnt, &occluded, filter);
+                    done = trav_other<ANY, STATS, EXT, LdsStack, TM, GBL_FUSE_NONE>(sc, st, stk, cnt, &occluded, filter);
                 }
             } else {
-                if (!trav_at_interior(st)) done = trav_other<ANY, STATS, EXT, LdsStack, TM, true>(sc, st, stk, cnt, &occluded, filter);
+                if (!trav_at_interior(st)) done = trav_other<ANY, STATS, EXT, LdsStack, TM, GBL_FUSE_LEAN>(sc, st, stk, cnt, &occluded, filter);
                 if (!done && trav_at_interior(st)) {
                     trav_interior<STATS, !ANY>(sc, st, stk, cnt);
                     if (STATS) ++steps;
@@ -423,7 +427,7 @@ __device__ __forceinline__ bool trace_quad(const DevScene& sc, bool want, F3 o, 
                 qdone = true;
                 (void)qstk;
             } else {   // the exit marker; analytic shapes; any-hit leaves of the instrumented builds
-                qdone = trav_other<ANY, STATS, EXT, LdsStack, TM, false>(sc, st, qstk, cnt, &qocc, filter);
+                qdone = trav_other<ANY, STATS, EXT, LdsStack, TM, GBL_FUSE_NONE>(sc, st, qstk, cnt, &qocc, filter);
             }
 #ifdef GBL_PHASE_CLOCK
             {   // wave-level: the iteration's time goes to the kind of the wave's first live quad

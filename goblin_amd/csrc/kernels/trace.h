@@ -102,8 +102,10 @@ __device__ __forceinline__ bool tri_test_regs(float4 q0, float4 q1, float4 q2, F
 // The three loads of a triangle record travel together: left alone the compiler sinks the p0 load below the `divisor == 0`
 // early-out, which makes every triangle test two dependent memory round trips instead of one (the traversal loops wait on
 // memory 43 % of their time, profiles/r03_bunny.json).  The empty asm needs all nine floats, so they are fetched ahead of it.
+// They are INPUTS of the asm only: as in-out operands the pin redefined the nine floats, and the triangle loop opened with a six-move
+// permutation of them (tools/loop_moves.py); the loads leave together, ahead of the test, either way.
 __device__ __forceinline__ void tri_fetch_together(float4& q0, float4& q1, float4& q2) {
-    asm volatile("" : "+v"(q0.x), "+v"(q0.y), "+v"(q0.z), "+v"(q1.x), "+v"(q1.y), "+v"(q1.z), "+v"(q2.x), "+v"(q2.y), "+v"(q2.z));
+    asm volatile("" ::"v"(q0.x), "v"(q0.y), "v"(q0.z), "v"(q1.x), "v"(q1.y), "v"(q1.z), "v"(q2.x), "v"(q2.y), "v"(q2.z));
 }
 __device__ __forceinline__ bool tri_test(const DevTri* tp, F3 o, F3 d, float mint, float maxt, float* t_out, float* b1_out,
                                          float* b2_out) {
@@ -423,39 +425,33 @@ __device__ __forceinline__ bool ref_reached(const DevScene& sc, int inst, uint32
 //                   headline kernel 32 %: a triangle is accepted 1.5 - 3 times per query, by a few lanes at a time.
 // `any`: the query kind as a value -- a compile-time constant through trav_other<ANY, ...> below.
 // FUSE: a leaf whose pop uncovers the instance's sentinel (and then, possibly, the exit marker) takes those steps at once instead
-// of spending an iteration of the caller's loop on each (needs st.world: the one-ray-per-lane loops only).
+// of spending an iteration of the caller's loop on each (needs st.world: the one-ray-per-lane loops only); GBL_FUSE_* below.
 #define GBL_TIE_NONE 0
 #define GBL_TIE_EXACT 1
 #define GBL_TIE_DETECT 2
-template <bool STATS, bool EXT, class STK, int TM, bool FUSE = false>
-__device__ __forceinline__ bool trav_other_kind(const DevScene& sc, TravState& st, const STK& stk, LaneCounters& cnt, const bool ANY,
-                                                bool* occluded, int filter) {
-    constexpr bool TIES = TM == GBL_TIE_EXACT;
-    const int cur = st.cur;
-    if (STATS) probe(cnt.oth_lane, cnt.oth_wave);
-    if (cur == GBL_STACK_EXIT) return true;
-    if (cur == GBL_STACK_SENTINEL) {   // finished an instance: back to the world ray
-        st.r = st.world;
-        st.inst = -1;
+// Entering an instance (st.cur is a TLAS leaf, st.inst < 0): the world ray through the instance's inverse transform.
+template <bool EXT, class STK>
+__device__ __forceinline__ void trav_enter(const DevScene& sc, TravState& st, const STK& stk, int filter) {
+    const uint32_t ref = ~static_cast<uint32_t>(st.cur);
+    const DevInstance* ip = sc.instances + (ref >> 2);
+    if (EXT && filter != GBL_FILTER_NONE && (ip->is_mask != 0u ? GBL_FILTER_MASK : GBL_FILTER_OPAQUE) != filter) {
         st.cur = static_cast<int>(stk.load(--st.sp));
-        return false;
+        return;
     }
-    const uint32_t ref = ~static_cast<uint32_t>(cur);
-    if (st.inst < 0) {
-        const DevInstance* ip = sc.instances + (ref >> 2);
-        if (EXT && filter != GBL_FILTER_NONE && (ip->is_mask != 0u ? GBL_FILTER_MASK : GBL_FILTER_OPAQUE) != filter) {
-            st.cur = static_cast<int>(stk.load(--st.sp));
-            return false;
-        }
-        // (A copy of every mesh instance's BLAS root node at an address that follows from the TLAS leaf alone, one word of it
-        //  fetched here next to the instance record so that the interior step behind this one finds the line on its way: no
-        //  gain -- configs[1] 42.4 against 42.1 ms, grid 20.8 / 20.8, AO 27.5 against 27.0.)
-        st.inst = static_cast<int>(ref >> 2);
-        ray_space(st.r, xf_point(ip->inv, st.world.o), xf_vector(ip->inv, st.world.d));
-        stk.store(st.sp++, GBL_STACK_SENTINEL);
-        st.cur = ip->root;
-        return false;
-    }
+    // (A copy of every mesh instance's BLAS root node at an address that follows from the TLAS leaf alone, one word of it
+    //  fetched here next to the instance record so that the interior step behind this one finds the line on its way: no
+    //  gain -- configs[1] 42.4 against 42.1 ms, grid 20.8 / 20.8, AO 27.5 against 27.0.)
+    st.inst = static_cast<int>(ref >> 2);
+    ray_space(st.r, xf_point(ip->inv, st.world.o), xf_vector(ip->inv, st.world.d));
+    stk.store(st.sp++, GBL_STACK_SENTINEL);
+    st.cur = ip->root;
+}
+// A leaf of the instance the ray is in (st.cur is a BLAS leaf or, EXT, an analytic shape; st.inst >= 0): tests it and pops the next
+// reference.  Reads st.r and never writes it.  Returns true when the query is finished (ANY: a triangle was accepted).
+template <bool STATS, bool EXT, class STK, int TM>
+__device__ __forceinline__ bool trav_leaf(const DevScene& sc, TravState& st, const STK& stk, LaneCounters& cnt, const bool ANY, bool* occluded) {
+    constexpr bool TIES = TM == GBL_TIE_EXACT;
+    const uint32_t ref = ~static_cast<uint32_t>(st.cur);
     const uint32_t first = ref >> 2, count = (ref & 3u) + 1u;
     if (EXT && first >= GBL_SHAPE_FIRST_DISK) {   // Model::intersect of an intersectable geometry (GoblinModel.cpp:46-54)
         const float radius = sc.instances[st.inst].radius;
@@ -533,17 +529,72 @@ __device__ __forceinline__ bool trav_other_kind(const DevScene& sc, TravState& s
         }
     }
     st.cur = static_cast<int>(stk.load(--st.sp));
-    if (FUSE) {
-        if (st.cur == GBL_STACK_SENTINEL) {
+    return false;
+}
+// One leaf / instance step, in one of three forms (FUSE):
+//   GBL_FUSE_NONE        one kind of step per call: exit marker, sentinel, instance entry or leaf
+//   GBL_FUSE_TAIL        the same, and a leaf (of triangles or, EXT, an analytic shape) whose pop uncovers the sentinel and then,
+//                        possibly, the exit marker takes those at once
+//   GBL_FUSE_LEAF_FIRST  the steps of GBL_FUSE_TAIL in an order that keeps the ray's registers where they are: the leaf, which only
+//                        READS st.r, stands ahead of both places that assign it, and ONE site leaves an instance -- for a sentinel met
+//                        at the top as for one the leaf's pop uncovers -- with the exit marker tested behind it; the entry comes last.
+//                        (Under GBL_FUSE_TAIL the sentinel's restore at the top is live across the leaf, so the merged ray gets
+//                        registers of its own and every lane copies its twelve floats there and back at every step: 26 moves beside
+//                        a triangle test of 60 in the lean quad kernels, DESIGN.md 4.1, tools/loop_moves.py.)
+// A ray's node visits and triangle tests are the same under all three.  GBL_FUSE_LEAN is the form of the lean one-ray-per-lane loops
+// (trace_loop, trace_quad's dense phase): leaf first, except in the units whose kernels it costs spilled registers (kernels_stream.hip;
+// the wavefront trace kernels, at 96 registers, stay with GBL_FUSE_TAIL for the same reason: profiles/trav_moves_ab.txt).
+#define GBL_FUSE_NONE 0
+#define GBL_FUSE_TAIL 1
+#define GBL_FUSE_LEAF_FIRST 2
+#ifndef GBL_FUSE_LEAN
+#define GBL_FUSE_LEAN GBL_FUSE_LEAF_FIRST
+#endif
+template <bool STATS, bool EXT, class STK, int TM, int FUSE = GBL_FUSE_NONE>
+__device__ __forceinline__ bool trav_other_kind(const DevScene& sc, TravState& st, const STK& stk, LaneCounters& cnt, const bool ANY,
+                                                bool* occluded, int filter) {
+    const int cur = st.cur;
+    if (STATS) probe(cnt.oth_lane, cnt.oth_wave);
+    if constexpr (FUSE != GBL_FUSE_LEAF_FIRST) {
+        if (cur == GBL_STACK_EXIT) return true;
+        if (cur == GBL_STACK_SENTINEL) {   // finished an instance: back to the world ray
             st.r = st.world;
             st.inst = -1;
             st.cur = static_cast<int>(stk.load(--st.sp));
+            return false;
         }
-        if (st.cur == GBL_STACK_EXIT) return true;
+        if (st.inst < 0) {
+            trav_enter<EXT>(sc, st, stk, filter);
+            return false;
+        }
+        if (trav_leaf<STATS, EXT, STK, TM>(sc, st, stk, cnt, ANY, occluded)) return true;
+        if (FUSE == GBL_FUSE_TAIL) {
+            if (st.cur == GBL_STACK_SENTINEL) {
+                st.r = st.world;
+                st.inst = -1;
+                st.cur = static_cast<int>(stk.load(--st.sp));
+            }
+            if (st.cur == GBL_STACK_EXIT) return true;
+        }
+        return false;
+    } else {
+        const bool marker = cur == GBL_STACK_SENTINEL || cur == GBL_STACK_EXIT;
+        const bool enter = !marker && st.inst < 0;
+        if (!marker && !enter && trav_leaf<STATS, EXT, STK, TM>(sc, st, stk, cnt, ANY, occluded)) return true;
+        if (!enter) {
+            if (st.cur == GBL_STACK_SENTINEL) {   // finished an instance: back to the world ray
+                st.r = st.world;
+                st.inst = -1;
+                st.cur = static_cast<int>(stk.load(--st.sp));
+            }
+            if (st.cur == GBL_STACK_EXIT) return true;
+        } else {
+            trav_enter<EXT>(sc, st, stk, filter);
+        }
+        return false;
     }
-    return false;
 }
-template <bool ANY, bool STATS, bool EXT, class STK, int TM, bool FUSE = false>
+template <bool ANY, bool STATS, bool EXT, class STK, int TM, int FUSE = GBL_FUSE_NONE>
 __device__ __forceinline__ bool trav_other(const DevScene& sc, TravState& st, const STK& stk, LaneCounters& cnt, bool* occluded,
                                            int filter = GBL_FILTER_NONE) {
     return trav_other_kind<STATS, EXT, STK, TM, FUSE>(sc, st, stk, cnt, ANY, occluded, filter);
@@ -615,7 +666,7 @@ __device__ __forceinline__ bool trace_loop(const DevScene& sc, F3 o, F3 d, float
                 break;
             }
         } else {
-            if (!trav_at_interior(st) && trav_other<ANY, STATS, EXT, STK, TM, true>(sc, st, stk, cnt, &occluded, filter)) break;
+            if (!trav_at_interior(st) && trav_other<ANY, STATS, EXT, STK, TM, GBL_FUSE_LEAN>(sc, st, stk, cnt, &occluded, filter)) break;
             if (trav_at_interior(st)) {
                 trav_interior<STATS, !ANY>(sc, st, stk, cnt);
                 if (STATS) ++steps;

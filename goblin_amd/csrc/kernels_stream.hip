@@ -1,5 +1,8 @@
 // libgoblin_hip.so, kernel unit: the path and AO kernels under GBL_SAMPLES_STREAM -- the reference's own per-tile
 // mt19937 sample stream generated on the device (kernels/stream.h, the STREAM instantiations of kernels/render_kernels.h).
+// (the lean loops' leaf / instance step stays in its tail-fused form here: leaf first, the one-ray-per-lane stream kernel spills 57
+//  vector registers for 54 -- kernels/trace.h GBL_FUSE_LEAN)
+#define GBL_FUSE_LEAN GBL_FUSE_TAIL
 #include "gbl_internal.h"
 #include "kernels/render_kernels.h"
 
