@@ -277,19 +277,18 @@ static gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32
         }
     std::vector<gbl_instance> edited = ctx->h_instances;
     for (uint32_t i = 0; i < count; ++i) edited[first + i].to_world = to_world[i];
-    std::vector<DevInstance> inst;
-    std::vector<DevNode> tlas;
-    int32_t root = 0;
-    int depth = 0;
-    float lo[3], hi[3];
+    const TlasInput in = {edited.data(),       static_cast<uint32_t>(edited.size()), ctx->h_meshes.data(),  ctx->h_materials.data(),
+                          ctx->mesh_lo.data(), ctx->mesh_hi.data(),                  ctx->mesh_root.data(), ctx->tlas_base};
+    TlasResult built;
     std::string err;
-    std::vector<DevInstanceBound> bounds;
-    gbl_status st = build_tlas(edited.data(), static_cast<uint32_t>(edited.size()), ctx->h_meshes.data(), ctx->h_materials.data(), ctx->mesh_lo.data(),
-                               ctx->mesh_hi.data(), ctx->mesh_root.data(), ctx->tlas_base, &inst, &tlas, &root, &depth, lo, hi, &err, &bounds);
+    gbl_status st = build_tlas(in, &built, &err);
     if (st != GBL_OK) {
         ctx->error = err;
         return st;
     }
+    const std::vector<DevInstance>& inst = built.instances;
+    const std::vector<DevNode>& tlas = built.nodes;
+    const std::vector<DevInstanceBound>& bounds = built.instance_bounds;
     if (tlas.size() > ctx->tlas_capacity) {
         ctx->error = "gbl_update_instances: rebuilt TLAS does not fit its reserved nodes";
         return GBL_ERR_DEVICE;
@@ -303,9 +302,9 @@ static gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32
         HIP_TRY(ctx, hipMemcpy(const_cast<DevInstanceBound*>(sc.instance_bounds), bounds.data(), bounds.size() * sizeof(DevInstanceBound), hipMemcpyHostToDevice));
     if (!tlas.empty())
         HIP_TRY(ctx, hipMemcpy(const_cast<DevNode*>(sc.nodes) + ctx->tlas_base, tlas.data(), tlas.size() * sizeof(DevNode), hipMemcpyHostToDevice));
-    sc.tlas_root = root;
-    sc.stack_entries = scene_stack_entries(tlas, ctx->tlas_base, root, inst, ctx->mesh_stack_need);   // (the wavefront stack backing is re-checked at render time)
-    ctx->info.tlas_depth = depth;
+    sc.tlas_root = built.root;
+    sc.stack_entries = scene_stack_entries(tlas, ctx->tlas_base, built.root, inst, ctx->mesh_stack_need);   // (the wavefront stack backing is re-checked at render time)
+    ctx->info.tlas_depth = built.depth;
     ctx->info.tlas_nodes = tlas.size();
     ctx->h_instances.swap(edited);
     ctx->auto_rays_per_path.clear();   // the edited scene's paths may be longer or shorter: AUTO measures again

@@ -13,6 +13,7 @@
 #include "scene_prep.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -129,13 +130,7 @@ void point_by(const Mat4& m, const float p[3], float out[3]) {
 
 // ---------------------------------------------------------------------- BVH
 struct Aabb {
-    float lo[3], hi[3];
-    Aabb() {
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = INFINITY;
-            hi[k] = -INFINITY;
-        }
-    }
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     void grow(const float p[3]) {
         for (int k = 0; k < 3; ++k) {
             lo[k] = std::min(lo[k], p[k]);
@@ -186,16 +181,19 @@ static bool stack_level_bound() {
     static const bool on = [] { const char* e = getenv("GBL_STACK_LEVEL_BOUND"); return e != nullptr && e[0] != '\0' && e[0] != '0'; }();
     return on;
 }
-static int blas_stack_need(const std::vector<DevNode>& nodes, int32_t ref) {
-    if (ref < 0 || ref >= static_cast<int32_t>(nodes.size())) return 0;   // a leaf (or an analytic shape's root)
-    const DevNode& n = nodes[static_cast<size_t>(ref)];
+template <class ChildNeed>
+static int node_stack_need(const DevNode& n, ChildNeed child_need) {
     int k = 0, deepest = 0;
     for (int c = 0; c < 4; ++c) {
         if (n.child[c] == GBL_REF_NONE) continue;
         ++k;
-        deepest = std::max(deepest, blas_stack_need(nodes, n.child[c]));
+        deepest = std::max(deepest, child_need(n.child[c]));
     }
     return k > 0 ? (stack_level_bound() ? 3 : k - 1) + deepest : 0;
+}
+static int blas_stack_need(const std::vector<DevNode>& nodes, int32_t ref) {
+    if (ref < 0 || ref >= static_cast<int32_t>(nodes.size())) return 0;   // a leaf (or an analytic shape's root)
+    return node_stack_need(nodes[static_cast<size_t>(ref)], [&](int32_t c) { return blas_stack_need(nodes, c); });
 }
 
 static int tlas_stack_need(const std::vector<DevNode>& tlas, int32_t tlas_base, int32_t ref, const std::vector<DevInstance>& instances,
@@ -210,14 +208,7 @@ static int tlas_stack_need(const std::vector<DevNode>& tlas, int32_t tlas_base, 
     }
     const size_t local = static_cast<size_t>(ref - tlas_base);
     if (local >= tlas.size()) return 0;
-    const DevNode& n = tlas[local];
-    int k = 0, deepest = 0;
-    for (int c = 0; c < 4; ++c) {
-        if (n.child[c] == GBL_REF_NONE) continue;
-        ++k;
-        deepest = std::max(deepest, tlas_stack_need(tlas, tlas_base, n.child[c], instances, mesh_need));
-    }
-    return k > 0 ? (stack_level_bound() ? 3 : k - 1) + deepest : 0;
+    return node_stack_need(tlas[local], [&](int32_t c) { return tlas_stack_need(tlas, tlas_base, c, instances, mesh_need); });
 }
 
 // SAH cost of visiting a node relative to one triangle test (tuning knob: GBL_SAH_CT)
@@ -495,9 +486,9 @@ struct Filter {
 };
 
 // Levels below a material slot: a constant is 0, a checkerboard / scale of constants is 1, ...  -1: bad index or cycle.
-int texture_depth(const gbl_scene_desc* d, int32_t id, int guard) {
-    if (id < 0 || static_cast<uint32_t>(id) >= d->num_textures || guard > 64) return -1;
-    const gbl_texture& g = d->textures[id];
+int texture_depth(const gbl_scene_desc& d, int32_t id, int guard) {
+    if (id < 0 || static_cast<uint32_t>(id) >= d.num_textures || guard > 64) return -1;
+    const gbl_texture& g = d.textures[id];
     if (g.type == GBL_TEX_CONSTANT) return 0;
     if (g.type == GBL_TEX_IMAGE) return 1;   // a leaf with a lookup of its own
     int a = texture_depth(d, g.child[0], guard + 1), b = texture_depth(d, g.child[1], guard + 1);
@@ -506,6 +497,211 @@ int texture_depth(const gbl_scene_desc* d, int32_t id, int guard) {
 }
 
 int ceil_i(float f) { return static_cast<int>(std::ceil(f)); }
+int floor_i(float f) { return static_cast<int>(std::floor(f)); }
+
+// ------------------------------------------------ what a check and a packer share
+// The arrays of one mesh inside the description's
+struct MeshView {
+    const float *P, *N, *uv;
+    const uint32_t* I;
+    const float* p(uint32_t t, int k) const { return P + 3 * I[3 * t + k]; }   // position, normal, uv of triangle t's vertex k
+    const float* n(uint32_t t, int k) const { return N + 3 * I[3 * t + k]; }
+    const float* t_uv(uint32_t t, int k) const { return uv + 2 * I[3 * t + k]; }
+};
+MeshView view_of(const gbl_scene_desc& d, const gbl_mesh& m) {
+    const size_t v = m.vertex_offset;
+    return MeshView{d.positions + 3 * v, d.normals + 3 * v, d.uvs + 2 * v, d.indices + 3 * static_cast<size_t>(m.tri_offset)};
+}
+
+// Per triangle of a mesh its vertices' bound (Triangle::getObjectBound), the bound's centre and its number
+std::vector<Prim> triangle_prims(const MeshView& mv, uint32_t n) {
+    std::vector<Prim> prims(n);
+    for (uint32_t t = 0; t < n; ++t) {
+        Prim& p = prims[t];
+        for (int k = 0; k < 3; ++k) p.box.grow(mv.p(t, k));
+        for (int k = 0; k < 3; ++k) p.c[k] = 0.5f * (p.box.lo[k] + p.box.hi[k]);
+        p.id = t;
+    }
+    return prims;
+}
+
+uint32_t tri_flags(const gbl_mesh& m) { return (m.has_normal ? 1u : 0u) | (m.has_uv ? 2u : 0u); }
+
+// The texture slots a material of this type reads (-1: none)
+std::array<int32_t, 6> texture_slots(const gbl_material& m) {
+    return {m.tex_color, m.tex_color2, m.tex_exponent, m.type == GBL_MAT_SUBSURFACE ? m.tex_color3 : -1, m.tex_bump, m.tex_normal};
+}
+
+// An instance's transform, or the one refusal build_tlas makes (validate_desc makes it first)
+bool instance_transform(const gbl_instance& gi, uint32_t i, Trs* t, std::string* err) {
+    *t = compose(gi.to_world.position, gi.to_world.orientation, gi.to_world.scale);
+    if (!t->invertible)
+        *err = "instance " + std::to_string(i) + ": |det(toWorld)| < 1e-5, the reference cannot invert this transform "
+               "(GoblinMatrix.cpp:451); use a uniform scale >= 0.0216";
+    return t->invertible;
+}
+
+uint64_t level_texels(const gbl_image& gi, uint32_t level) {
+    return static_cast<uint64_t>(std::max(1u, gi.width >> level)) * std::max(1u, gi.height >> level) * gi.channels;
+}
+
+// The medium's box (BBox(p1, p2), GoblinBBox.h:20-23) and its transform
+struct VolumeRegion { float lo[3], hi[3]; Trs to_world; };
+VolumeRegion region_of(const gbl_volume& g) {
+    VolumeRegion r;
+    for (int k = 0; k < 3; ++k) r.lo[k] = std::min(g.box_min[k], g.box_max[k]), r.hi[k] = std::max(g.box_min[k], g.box_max[k]);
+    r.to_world = compose(g.to_world.position, g.to_world.orientation, g.to_world.scale);
+    return r;
+}
+// The region's longest world-space diagonal: a march is at most this / step_size points long
+double march_diagonal(const VolumeRegion& r) {
+    double diag = 0.0;
+    for (int sgn = 0; sgn < 4; ++sgn) {
+        const double e[3] = {double(r.hi[0] - r.lo[0]), (sgn & 1 ? -1.0 : 1.0) * double(r.hi[1] - r.lo[1]), (sgn & 2 ? -1.0 : 1.0) * double(r.hi[2] - r.lo[2])};
+        double w[3];
+        for (int k = 0; k < 3; ++k) w[k] = r.to_world.m.v[k][0] * e[0] + r.to_world.m.v[k][1] * e[1] + r.to_world.m.v[k][2] * e[2];
+        diag = std::max(diag, std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]));
+    }
+    return diag;
+}
+
+void store_bound(const Aabb& b, float lo[3], float hi[3]) {
+    for (int k = 0; k < 3; ++k) lo[k] = b.lo[k], hi[k] = b.hi[k];
+}
+
+int filter_halo(const gbl_film& f) { return ceil_i(std::max(f.filter_width[0], f.filter_width[1]) + 0.5f); }
+
+// ---------------------------------------------------------------- validation
+gbl_status refuse(gbl_status st, const std::string& why, std::string* err) { *err = why; return st; }
+
+gbl_status validate_meshes(const gbl_scene_desc& d, std::string* err) {
+    for (uint32_t i = 0; i < d.num_meshes; ++i) {
+        const gbl_mesh& m = d.meshes[i];
+        const std::string who = "mesh " + std::to_string(i);
+        if (m.shape == GBL_SHAPE_SPHERE || m.shape == GBL_SHAPE_DISK) continue;
+        if (m.shape != GBL_SHAPE_MESH) return refuse(GBL_ERR_INVALID, who + " has an unknown shape", err);
+        if (m.tri_count == 0 || static_cast<uint64_t>(m.vertex_offset) + m.vertex_count > d.num_vertices || static_cast<uint64_t>(m.tri_offset) + m.tri_count > d.num_triangles)
+            return refuse(GBL_ERR_INVALID, who + " is empty or out of range", err);
+        const MeshView mv = view_of(d, m);
+        for (uint32_t t = 0; t < 3 * m.tri_count; ++t)
+            if (mv.I[t] >= m.vertex_count) return refuse(GBL_ERR_INVALID, who + " has a vertex index out of range", err);
+        if (!m.has_uv) continue;
+        // A triangle whose uv determinant is 0 makes the reference build its tangent from whatever Fragment the caller passed in
+        // (GoblinTriangle.cpp:113-117): not reproducible.
+        for (uint32_t t = 0; t < m.tri_count; ++t) {
+            const float *a = mv.t_uv(t, 0), *b = mv.t_uv(t, 1), *c = mv.t_uv(t, 2);
+            float du1 = b[0] - a[0], dv1 = b[1] - a[1], du2 = c[0] - a[0], dv2 = c[1] - a[1];
+            if (du1 * dv2 - dv1 * du2 == 0.0f)
+                return refuse(GBL_ERR_UNSUPPORTED, who + " triangle " + std::to_string(t) + " has degenerate texture coordinates (stale-fragment branch of the reference)", err);
+        }
+    }
+    return GBL_OK;
+}
+
+gbl_status validate_materials(const gbl_scene_desc& d, std::string* err) {
+    for (uint32_t i = 0; i < d.num_materials; ++i) {
+        const gbl_material& m = d.materials[i];
+        if (m.type > GBL_MAT_SUBSURFACE) return refuse(GBL_ERR_INVALID, "unknown material type", err);
+        if (m.type == GBL_MAT_MASK && (m.masked_material < 0 || static_cast<uint32_t>(m.masked_material) >= d.num_materials ||
+                                       d.materials[m.masked_material].type == GBL_MAT_MASK || d.materials[m.masked_material].type == GBL_MAT_SUBSURFACE))
+            return refuse(GBL_ERR_INVALID, "mask material " + std::to_string(i) + " must wrap a non-mask, non-subsurface material of the scene", err);
+        for (int32_t t : texture_slots(m)) {
+            if (t < 0) continue;
+            const int depth = texture_depth(d, t, 0);
+            if (depth < 0)
+                return refuse(GBL_ERR_INVALID, "material " + std::to_string(i) + " references a texture out of range (or a cyclic texture graph)", err);
+            if (depth > GBL_TEX_MAX_DEPTH)
+                return refuse(GBL_ERR_UNSUPPORTED, "material " + std::to_string(i) + ": texture graph deeper than " +
+                              std::to_string(GBL_TEX_MAX_DEPTH) + " levels below the material slot is outside the device path", err);
+        }
+    }
+    return GBL_OK;
+}
+
+gbl_status validate_images(const gbl_scene_desc& d, std::string* err) {
+    for (uint32_t i = 0; i < d.num_images; ++i) {
+        const gbl_image& gi = d.images[i];
+        if (gi.width == 0 || gi.height == 0 || (gi.width & (gi.width - 1)) || (gi.height & (gi.height - 1)) || (gi.channels != 1 && gi.channels != 4) ||
+            gi.levels == 0 || gi.levels > 18)
+            return refuse(GBL_ERR_INVALID, "image " + std::to_string(i) + ": sides must be powers of two, channels 1 or 4, at most 18 levels", err);
+        uint64_t texels = 0;
+        for (uint32_t l = 0; l < gi.levels; ++l) texels += level_texels(gi, l);
+        if (gi.texel_offset + texels > d.num_texels || texels >= (1ull << 32))
+            return refuse(GBL_ERR_INVALID, "image " + std::to_string(i) + ": texels out of range", err);
+    }
+    return GBL_OK;
+}
+
+gbl_status validate_textures(const gbl_scene_desc& d, std::string* err) {
+    for (uint32_t i = 0; i < d.num_textures; ++i) {
+        const gbl_texture& g = d.textures[i];
+        if (g.type > GBL_TEX_IMAGE || g.mapping > GBL_MAP_SPHERICAL) return refuse(GBL_ERR_INVALID, "unknown texture or mapping type", err);
+        if (g.type == GBL_TEX_IMAGE && (g.image < 0 || static_cast<uint32_t>(g.image) >= d.num_images || g.image_filter > GBL_IMAGE_FILTER_EWA ||
+                                        g.address > GBL_ADDRESS_BORDER || d.images[g.image].channels != (g.is_float ? 1u : 4u)))
+            return refuse(GBL_ERR_INVALID, "image texture " + std::to_string(i) + ": bad image index, filter, address mode or channel count", err);
+    }
+    return GBL_OK;
+}
+
+gbl_status validate_lights(const gbl_scene_desc& d, std::string* err) {
+    for (uint32_t i = 0; i < d.num_lights; ++i) {
+        const gbl_light& gl = d.lights[i];
+        if (gl.type == GBL_LIGHT_AREA && gl.mesh >= d.num_meshes) return refuse(GBL_ERR_INVALID, "area light references a mesh out of range", err);
+        if (gl.type == GBL_LIGHT_IBL && (gl.image < 0 || static_cast<uint32_t>(gl.image) >= d.num_images || d.images[gl.image].channels != 4))
+            return refuse(GBL_ERR_INVALID, "image based light " + std::to_string(i) + ": bad image index", err);
+        if (gl.type > GBL_LIGHT_IBL) return refuse(GBL_ERR_INVALID, "unknown light type", err);
+    }
+    return GBL_OK;
+}
+
+gbl_status validate_volume(const gbl_volume& g, std::string* err) {
+    if (g.type == GBL_VOLUME_NONE || g.type == GBL_VOLUME_HOMOGENEOUS) return GBL_OK;
+    if (g.type != GBL_VOLUME_HETEROGENEOUS) return refuse(GBL_ERR_INVALID, "unknown volume type", err);
+    if (g.grid[0] <= 0 || g.grid[1] <= 0 || g.grid[2] <= 0 || (g.grid_channels != 1 && g.grid_channels != 3) || g.density == nullptr)
+        return refuse(GBL_ERR_INVALID, "heterogeneous volume: the density grid needs positive dimensions, 1 or 3 channels and its data", err);
+    // the march loops of kernels/medium.h advance t by step_size: zero, negative, NaN or a step below the float spacing
+    // of t never terminates -- a spin on the reference's CPU, an unrecoverable hang on a GPU
+    if (!(g.step_size > 0.0f) || !std::isfinite(g.step_size))
+        return refuse(GBL_ERR_INVALID, "heterogeneous volume: step_size must be a positive finite number", err);
+    // the device indexes the grid with 32-bit ints
+    const uint64_t cells = static_cast<uint64_t>(g.grid[0]) * static_cast<uint64_t>(g.grid[1]);
+    if (cells > (1ull << 31) || cells * static_cast<uint64_t>(g.grid[2]) > (1ull << 31) ||
+        cells * static_cast<uint64_t>(g.grid[2]) * static_cast<uint64_t>(g.grid_channels) >= (1ull << 31))
+        return refuse(GBL_ERR_INVALID, "heterogeneous volume: the density grid holds 2^31 values or more", err);
+    // bounded at the 10^6 points the stream sampler's draw budget assumes (api_render.hip medium_draws_per_sample) -- a step
+    // of 1e-12 is a hang, not a render
+    if (!(march_diagonal(region_of(g)) / double(g.step_size) <= 1.0e6))
+        return refuse(GBL_ERR_INVALID, "heterogeneous volume: step_size is too small for the region (more than 10^6 steps across it)", err);
+    return GBL_OK;
+}
+
+gbl_status validate_film(const gbl_film& f, std::string* err) {
+    if (f.xres <= 0 || f.yres <= 0) return refuse(GBL_ERR_INVALID, "film resolution must be positive", err);
+    if (!(f.filter_width[0] > 0.0f) || !(f.filter_width[1] > 0.0f) || filter_halo(f) > GBL_MAX_FILTER_HALO)
+        return refuse(GBL_ERR_UNSUPPORTED, "filter width must be in (0, " + std::to_string(GBL_MAX_FILTER_HALO - 0.5f) + "] pixels", err);
+    return GBL_OK;
+}
+
+// Every refusal pack_scene makes, in a fixed order (a description with two faults reports the earlier section's), before
+// anything is packed: writes nothing but *err.
+gbl_status validate_desc(const gbl_scene_desc* d, std::string* err) {
+    if (!d || d->abi_version != GBL_ABI_VERSION) return refuse(GBL_ERR_INVALID, "scene description has the wrong abi_version", err);
+    if (d->camera.type > GBL_CAMERA_ORTHOGRAPHIC) return refuse(GBL_ERR_INVALID, "unknown camera type", err);
+    for (uint32_t i = 0; i < d->num_instances; ++i)
+        if (d->instances[i].mesh >= d->num_meshes || d->instances[i].material >= d->num_materials || d->instances[i].area_light >= static_cast<int32_t>(d->num_lights))
+            return refuse(GBL_ERR_INVALID, "instance " + std::to_string(i) + " references a mesh/material/light out of range", err);
+    gbl_status st = validate_meshes(*d, err);
+    Trs t;
+    for (uint32_t i = 0; i < d->num_instances && st == GBL_OK; ++i)
+        if (!instance_transform(d->instances[i], i, &t, err)) st = GBL_ERR_INVALID;
+    if (st == GBL_OK) st = validate_materials(*d, err);
+    if (st == GBL_OK) st = validate_images(*d, err);
+    if (st == GBL_OK) st = validate_textures(*d, err);
+    if (st == GBL_OK) st = validate_lights(*d, err);
+    if (st == GBL_OK) st = validate_volume(d->volume, err);
+    if (st == GBL_OK) st = validate_film(d->film, err);
+    return st;
+}
 
 }  // namespace
 
@@ -515,39 +711,32 @@ int scene_stack_entries(const std::vector<DevNode>& tlas, int32_t tlas_base, int
 }
 
 // Instances (transforms in the reference's float order, world boxes by Transform::onBBox) and the TLAS over them.
-// TLAS node k gets device index tlas_base + k; sb_lo/hi return the union of the instance boxes.
-gbl_status build_tlas(const gbl_instance* inst, uint32_t n, const gbl_mesh* meshes, const gbl_material* materials, const float* mesh_lo,
-                      const float* mesh_hi, const int32_t* mesh_root, int32_t tlas_base, std::vector<DevInstance>* out_inst,
-                      std::vector<DevNode>* out_nodes, int32_t* tlas_root, int* tlas_depth, float sb_lo[3], float sb_hi[3], std::string* err,
-                      std::vector<DevInstanceBound>* bounds_out) {
+// TLAS node k gets device index tlas_base + k; bound_lo/hi return the union of the instance boxes.
+gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err) {
     const int kTlasCap = 22;
-    if (bounds_out) bounds_out->clear();
-    out_inst->resize(n);
-    out_nodes->clear();
-    std::vector<Prim> iprims(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const gbl_instance& gi = inst[i];
-        Trs t = compose(gi.to_world.position, gi.to_world.orientation, gi.to_world.scale);
-        if (!t.invertible) {
-            *err = "instance " + std::to_string(i) + ": |det(toWorld)| < 1e-5, the reference cannot invert this transform "
-                   "(GoblinMatrix.cpp:451); use a uniform scale >= 0.0216";
-            return GBL_ERR_INVALID;
-        }
-        DevInstance& di = (*out_inst)[i];
+    out->instances.resize(in.count);
+    out->instance_bounds.resize(in.count);
+    out->nodes.clear();
+    std::vector<Prim> iprims(in.count);
+    Aabb scene_bound;
+    for (uint32_t i = 0; i < in.count; ++i) {
+        const gbl_instance& gi = in.instances[i];
+        Trs t;
+        if (!instance_transform(gi, i, &t, err)) return GBL_ERR_INVALID;
+        DevInstance& di = out->instances[i];
         memset(&di, 0, sizeof(di));
         store3x4(t.m, di.m);
         store3x4(t.inv, di.inv);
-        di.root = mesh_root[gi.mesh];
+        di.root = in.mesh_root[gi.mesh];
         di.material = static_cast<int32_t>(gi.material);
         di.area_light = gi.area_light;
         di.mesh = static_cast<int32_t>(gi.mesh);
-        di.shape = meshes[gi.mesh].shape;
-        di.radius = meshes[gi.mesh].radius;
+        di.shape = in.meshes[gi.mesh].shape;
+        di.radius = in.meshes[gi.mesh].radius;
         // MaskMaterial ORs BSDFnullptr into its type; SubsurfaceMaterial's type is BSDFAll, which holds the bit as well
-        di.is_mask = (materials[gi.material].type == GBL_MAT_MASK || materials[gi.material].type == GBL_MAT_SUBSURFACE) ? 1u : 0u;
+        di.is_mask = (in.materials[gi.material].type == GBL_MAT_MASK || in.materials[gi.material].type == GBL_MAT_SUBSURFACE) ? 1u : 0u;
         // Transform::onBBox: the 8 corners of the mesh bound
-        const float* lo = mesh_lo + 3 * gi.mesh;
-        const float* hi = mesh_hi + 3 * gi.mesh;
+        const float *lo = in.mesh_lo + 3 * gi.mesh, *hi = in.mesh_hi + 3 * gi.mesh;
         Prim& p = iprims[i];
         for (int c = 0; c < 8; ++c) {
             float corner[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
@@ -556,98 +745,24 @@ gbl_status build_tlas(const gbl_instance* inst, uint32_t n, const gbl_mesh* mesh
             p.box.grow(w);
         }
         for (int k = 0; k < 3; ++k) p.c[k] = 0.5f * (p.box.lo[k] + p.box.hi[k]);
+        store_bound(p.box, out->instance_bounds[i].lo, out->instance_bounds[i].hi);
         p.id = i;
-        if (bounds_out) {
-            DevInstanceBound wb;
-            for (int k = 0; k < 3; ++k) {
-                wb.lo[k] = p.box.lo[k];
-                wb.hi[k] = p.box.hi[k];
-            }
-            bounds_out->push_back(wb);
-        }
-    }
-    Aabb scene_bound;
-    for (const Prim& p : iprims) {
         scene_bound.grow(p.box.lo);
         scene_bound.grow(p.box.hi);
     }
-    for (int k = 0; k < 3; ++k) {
-        sb_lo[k] = scene_bound.lo[k];
-        sb_hi[k] = scene_bound.hi[k];
-    }
-    *tlas_depth = 0;
-    *tlas_root = 0;
-    if (n > 0) {
+    store_bound(scene_bound, out->bound_lo, out->bound_hi);
+    out->depth = 0;
+    out->root = 0;
+    if (in.count > 0) {
         Builder tb(iprims, 1, kTlasCap);
         int root = tb.build(0, iprims.size(), 1);
-        Flat4 t4(tb, *out_nodes, tlas_base);
+        Flat4 t4(tb, out->nodes, in.tlas_base);
         auto inst_ref = [&](uint32_t first, uint32_t) { return ~static_cast<int32_t>(iprims[first].id << 2); };
-        *tlas_root = t4.emit(root, 1, inst_ref);
-        *tlas_depth = t4.depth;
+        out->root = t4.emit(root, 1, inst_ref);
+        out->depth = t4.depth;
     }
     return GBL_OK;
 }
-
-namespace {
-int floor_i(float f) { return static_cast<int>(std::floor(f)); }
-
-}  // namespace
-
-// BVH::buildLinearBVH (GoblinBVH.cpp:81-151) with the EqualCount split, followed only as far as the SHAPE of the tree:
-// per triangle the root-to-leaf path, the split axes along it and its place in a multi-triangle leaf.
-namespace {
-struct RefItem {   // BVHPrimitiveInfo (:8-14)
-    float lo[3], hi[3], c[3];
-    uint32_t id;
-};
-void reference_order_rec(std::vector<RefItem>& it, uint32_t start, uint32_t end, uint32_t depth, uint32_t path, uint64_t axes,
-                         DevTriOrder* out) {
-    auto leaf = [&]() {
-        for (uint32_t i = start; i < end; ++i) {
-            DevTriOrder& o = out[it[i].id];
-            o.path = path;
-            o.axes_lo = static_cast<uint32_t>(axes);
-            o.axes_hi = static_cast<uint32_t>(axes >> 32);
-            o.depth_rank = depth | ((i - start) << 8);
-        }
-    };
-    if (end - start == 1 || depth >= 32) return leaf();
-    float clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t i = start; i < end; ++i)
-        for (int k = 0; k < 3; ++k) {
-            clo[k] = std::min(clo[k], it[i].c[k]);
-            chi[k] = std::max(chi[k], it[i].c[k]);
-        }
-    const float dx = chi[0] - clo[0], dy = chi[1] - clo[1], dz = chi[2] - clo[2];
-    const int dim = (dx > dy && dx > dz) ? 0 : (dy > dz ? 1 : 2);   // BBox::longestAxis, GoblinBBox.cpp:79-88
-    if (clo[dim] == chi[dim]) return leaf();
-    const uint32_t mid = (start + end) / 2;
-    std::nth_element(&it[start], &it[mid], &it[end - 1] + 1, [dim](const RefItem& a, const RefItem& b) { return a.c[dim] < b.c[dim]; });
-    axes |= static_cast<uint64_t>(dim) << (2 * depth);
-    reference_order_rec(it, start, mid, depth + 1, path, axes, out);
-    reference_order_rec(it, mid, end, depth + 1, path | (1u << depth), axes, out);
-}
-void reference_order(const float* P, const uint32_t* I, uint32_t n, DevTriOrder* out) {
-    std::vector<RefItem> it(n);
-    for (uint32_t t = 0; t < n; ++t) {
-        RefItem& r = it[t];
-        for (int k = 0; k < 3; ++k) {
-            r.lo[k] = INFINITY;
-            r.hi[k] = -INFINITY;
-        }
-        for (int v = 0; v < 3; ++v) {   // Triangle::getObjectBound: the three vertices' bound
-            const float* p = P + 3 * I[3 * t + v];
-            for (int k = 0; k < 3; ++k) {
-                r.lo[k] = std::min(r.lo[k], p[k]);
-                r.hi[k] = std::max(r.hi[k], p[k]);
-            }
-        }
-        for (int k = 0; k < 3; ++k) r.c[k] = 0.5f * (r.lo[k] + r.hi[k]);
-        r.id = t;
-    }
-    reference_order_rec(it, 0, n, 0, 0u, 0ull, out);
-}
-}   // namespace
 
 bool camera_extended(const gbl_camera& c) { return c.lens_radius != 0.0f || c.type != GBL_CAMERA_PERSPECTIVE; }
 
@@ -669,217 +784,170 @@ void pack_camera(const gbl_camera& c, const gbl_film& film, DevCamera* out) {
     out->film_h = c.film_width / aspect;
 }
 
-gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* err, bool device_blas) {
-    if (!d || d->abi_version != GBL_ABI_VERSION) {
-        *err = "scene description has the wrong abi_version";
-        return GBL_ERR_INVALID;
-    }
-    out->extended = 0;   // the scene's part first; the camera's is added where the camera is packed
-    if (d->camera.type > GBL_CAMERA_ORTHOGRAPHIC) {
-        *err = "unknown camera type";
-        return GBL_ERR_INVALID;
-    }
-    for (uint32_t i = 0; i < d->num_instances; ++i) {
-        if (d->instances[i].mesh >= d->num_meshes || d->instances[i].material >= d->num_materials ||
-            d->instances[i].area_light >= static_cast<int32_t>(d->num_lights)) {
-            *err = "instance " + std::to_string(i) + " references a mesh/material/light out of range";
-            return GBL_ERR_INVALID;
-        }
-    }
-    for (uint32_t i = 0; i < d->num_meshes; ++i) {
-        const gbl_mesh& m = d->meshes[i];
-        if (m.shape == GBL_SHAPE_SPHERE || m.shape == GBL_SHAPE_DISK) {
-            out->extended = 1;
-            continue;
-        }
-        if (m.shape != GBL_SHAPE_MESH) {
-            *err = "mesh " + std::to_string(i) + " has an unknown shape";
-            return GBL_ERR_INVALID;
-        }
-        if (m.tri_count == 0 || static_cast<uint64_t>(m.vertex_offset) + m.vertex_count > d->num_vertices ||
-            static_cast<uint64_t>(m.tri_offset) + m.tri_count > d->num_triangles) {
-            *err = "mesh " + std::to_string(i) + " is empty or out of range";
-            return GBL_ERR_INVALID;
-        }
-        for (uint32_t t = 0; t < 3 * m.tri_count; ++t)
-            if (d->indices[3 * static_cast<size_t>(m.tri_offset) + t] >= m.vertex_count) {
-                *err = "mesh " + std::to_string(i) + " has a vertex index out of range";
-                return GBL_ERR_INVALID;
-            }
-        if (m.has_uv) {
-            // A triangle whose uv determinant is 0 makes the reference build its tangent from
-            // whatever Fragment the caller passed in (GoblinTriangle.cpp:113-117): not reproducible.
-            const float* uv = d->uvs + 2 * static_cast<size_t>(m.vertex_offset);
-            const uint32_t* I = d->indices + 3 * static_cast<size_t>(m.tri_offset);
-            for (uint32_t t = 0; t < m.tri_count; ++t) {
-                const float* a = uv + 2 * I[3 * t];
-                const float* b = uv + 2 * I[3 * t + 1];
-                const float* c = uv + 2 * I[3 * t + 2];
-                float du1 = b[0] - a[0], dv1 = b[1] - a[1], du2 = c[0] - a[0], dv2 = c[1] - a[1];
-                if (du1 * dv2 - dv1 * du2 == 0.0f) {
-                    *err = "mesh " + std::to_string(i) + " triangle " + std::to_string(t) +
-                           " has degenerate texture coordinates (stale-fragment branch of the reference)";
-                    return GBL_ERR_UNSUPPORTED;
-                }
-            }
-        }
-    }
+// ------------------------------------------------------------------ geometry
+namespace {
 
-    // ---- vertex attributes used at shading time
-    out->positions.assign(d->positions, d->positions + 3 * static_cast<size_t>(d->num_vertices));
-    out->normals.assign(d->normals, d->normals + 3 * static_cast<size_t>(d->num_vertices));
-    out->uvs.assign(d->uvs, d->uvs + 2 * static_cast<size_t>(d->num_vertices));
+// BVH::buildLinearBVH (GoblinBVH.cpp:81-151) with the EqualCount split, followed only as far as the SHAPE of the tree:
+// per triangle the root-to-leaf path, the split axes along it and its place in a multi-triangle leaf.
+void reference_order(std::vector<Prim>& it, uint32_t start, uint32_t end, uint32_t depth, uint32_t path, uint64_t axes, DevTriOrder* out) {
+    auto leaf = [&]() {
+        for (uint32_t i = start; i < end; ++i) {
+            DevTriOrder& o = out[it[i].id];
+            o.path = path;
+            o.axes_lo = static_cast<uint32_t>(axes);
+            o.axes_hi = static_cast<uint32_t>(axes >> 32);
+            o.depth_rank = depth | ((i - start) << 8);
+        }
+    };
+    if (end - start == 1 || depth >= 32) return leaf();
+    float clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t i = start; i < end; ++i)
+        for (int k = 0; k < 3; ++k) {
+            clo[k] = std::min(clo[k], it[i].c[k]);
+            chi[k] = std::max(chi[k], it[i].c[k]);
+        }
+    const float dx = chi[0] - clo[0], dy = chi[1] - clo[1], dz = chi[2] - clo[2];
+    const int dim = (dx > dy && dx > dz) ? 0 : (dy > dz ? 1 : 2);   // BBox::longestAxis, GoblinBBox.cpp:79-88
+    if (clo[dim] == chi[dim]) return leaf();
+    const uint32_t mid = (start + end) / 2;
+    std::nth_element(&it[start], &it[mid], &it[end - 1] + 1, [dim](const Prim& a, const Prim& b) { return a.c[dim] < b.c[dim]; });
+    axes |= static_cast<uint64_t>(dim) << (2 * depth);
+    reference_order(it, start, mid, depth + 1, path, axes, out);
+    reference_order(it, mid, end, depth + 1, path | (1u << depth), axes, out);
+}
+// The vertex attributes used at shading time
+void pack_attributes(const gbl_scene_desc& d, PackedScene* out) {
+    out->positions.assign(d.positions, d.positions + 3 * static_cast<size_t>(d.num_vertices));
+    out->normals.assign(d.normals, d.normals + 3 * static_cast<size_t>(d.num_vertices));
+    out->uvs.assign(d.uvs, d.uvs + 2 * static_cast<size_t>(d.num_vertices));
+}
 
-    // ---- the reference's visiting order of every mesh's triangles (DevTriOrder)
-    out->tri_order.assign(d->num_triangles, DevTriOrder());
-    for (uint32_t mi = 0; mi < d->num_meshes; ++mi) {
-        const gbl_mesh& gm = d->meshes[mi];
-        if (gm.shape != GBL_SHAPE_MESH || gm.tri_count == 0) continue;
-        reference_order(d->positions + 3 * static_cast<size_t>(gm.vertex_offset), d->indices + 3 * static_cast<size_t>(gm.tri_offset),
-                        gm.tri_count, out->tri_order.data() + gm.tri_offset);
-    }
-
-    // ---- every triangle's own bound (the reference BLAS's leaf boxes, DevTriBound)
-    out->tri_bounds.assign(d->num_triangles, DevTriBound());
-    for (uint32_t mi = 0; mi < d->num_meshes; ++mi) {
-        const gbl_mesh& gm = d->meshes[mi];
+// Per triangle of every mesh: the reference's visiting order (DevTriOrder) and the triangle's own bound (the reference
+// BLAS's leaf boxes, DevTriBound)
+void pack_tri_order_and_bounds(const gbl_scene_desc& d, PackedScene* out) {
+    out->tri_order.assign(d.num_triangles, DevTriOrder());
+    out->tri_bounds.assign(d.num_triangles, DevTriBound());
+    for (uint32_t mi = 0; mi < d.num_meshes; ++mi) {
+        const gbl_mesh& gm = d.meshes[mi];
         if (gm.shape != GBL_SHAPE_MESH) continue;
-        const float* P = d->positions + 3 * static_cast<size_t>(gm.vertex_offset);
-        const uint32_t* I = d->indices + 3 * static_cast<size_t>(gm.tri_offset);
+        const MeshView mv = view_of(d, gm);
+        std::vector<Prim> items = triangle_prims(mv, gm.tri_count);   // BVHPrimitiveInfo (GoblinBVH.cpp:8-14)
+        reference_order(items, 0, gm.tri_count, 0, 0u, 0ull, out->tri_order.data() + gm.tri_offset);
         for (uint32_t t = 0; t < gm.tri_count; ++t) {
             DevTriBound& b = out->tri_bounds[gm.tri_offset + t];
             memset(&b, 0, sizeof(b));
-            const float *a = P + 3 * I[3 * t], *bb = P + 3 * I[3 * t + 1], *c = P + 3 * I[3 * t + 2];
+            const float *a = mv.p(t, 0), *bb = mv.p(t, 1), *c = mv.p(t, 2);
             for (int k = 0; k < 3; ++k) {
                 b.lo[k] = std::min(std::min(a[k], bb[k]), c[k]);
                 b.hi[k] = std::max(std::max(a[k], bb[k]), c[k]);
             }
         }
     }
+}
 
-    // ---- one BLAS per mesh
+// The SAH tree over one mesh's triangles, appended to `nodes`, and its triangles in leaf order, appended to `tris`
+void build_host_blas(const gbl_mesh& gm, const MeshView& mv, uint32_t mi, PackedScene* out) {
     const int kBlasCap = 40;
-    std::vector<int32_t> mesh_root(d->num_meshes);
-    std::vector<Aabb> mesh_bounds(d->num_meshes);
-    out->tris.clear();
-    out->tri_shade.assign(d->num_triangles, DevTriShade());
-    out->blas_max_depth = 0;
-    out->mesh_stack_need.assign(d->num_meshes, 0);
-    for (uint32_t mi = 0; mi < d->num_meshes; ++mi) {
-        const gbl_mesh& gm = d->meshes[mi];
-        if (gm.shape != GBL_SHAPE_MESH) {
-            // Sphere / Disk::getObjectBound (GoblinSphere.cpp:140-143, GoblinDisk.cpp:81-84); no BLAS: the
-            // instance's root is a marker reference and the traversal tests the shape analytically
-            const float r = gm.radius, z = gm.shape == GBL_SHAPE_SPHERE ? gm.radius : 0.0f;
-            float hi[3] = {r, r, z}, lo[3] = {-r, -r, -z};
-            mesh_bounds[mi].grow(hi);
-            mesh_bounds[mi].grow(lo);
-            mesh_root[mi] = gm.shape == GBL_SHAPE_SPHERE ? GBL_REF_SPHERE : GBL_REF_DISK;
-            continue;
-        }
-        const float* P = d->positions + 3 * static_cast<size_t>(gm.vertex_offset);
-        const uint32_t* I = d->indices + 3 * static_cast<size_t>(gm.tri_offset);
-        for (uint32_t v = 0; v < gm.vertex_count; ++v) mesh_bounds[mi].grow(P + 3 * v);
-        if (device_blas) {   // shading records only; the tree and the DevTri order come from kernels/lbvh.h
-            for (uint32_t t = 0; t < gm.tri_count; ++t) {
-                DevTriShade& s = out->tri_shade[gm.tri_offset + t];
-                for (int k = 0; k < 3; ++k) s.v[k] = gm.vertex_offset + I[3 * t + k];
-                s.flags = (gm.has_normal ? 1u : 0u) | (gm.has_uv ? 2u : 0u);
-            }
-            mesh_root[mi] = 0;
-            continue;
-        }
-        std::vector<Prim> prims(gm.tri_count);
-        for (uint32_t t = 0; t < gm.tri_count; ++t) {
-            Prim& p = prims[t];
-            for (int k = 0; k < 3; ++k) p.box.grow(P + 3 * I[3 * t + k]);
-            for (int k = 0; k < 3; ++k) p.c[k] = 0.5f * (p.box.lo[k] + p.box.hi[k]);
-            p.id = t;
-            DevTriShade& s = out->tri_shade[gm.tri_offset + t];
-            for (int k = 0; k < 3; ++k) s.v[k] = gm.vertex_offset + I[3 * t + k];
-            s.flags = (gm.has_normal ? 1u : 0u) | (gm.has_uv ? 2u : 0u);
-        }
-        const int leaf_knob = [] { const char* e = getenv("GBL_MAX_LEAF"); return e ? std::max(1, std::min(GBL_MAX_LEAF_TRIS, atoi(e))) : GBL_MAX_LEAF_TRIS; }();
-        Builder b(prims, leaf_knob, kBlasCap);
-        int root = b.build_parallel(prims.size());
-        Flat4 f4(b, out->nodes);
-        uint32_t tri_base = static_cast<uint32_t>(out->tris.size());
-        for (const Prim& p : prims) {
-            const float* p0 = P + 3 * I[3 * p.id];
-            const float* p1 = P + 3 * I[3 * p.id + 1];
-            const float* p2 = P + 3 * I[3 * p.id + 2];
-            DevTri t;
-            memset(&t, 0, sizeof(t));
-            for (int k = 0; k < 3; ++k) {
-                t.p0[k] = p0[k];
-                t.e1[k] = p1[k] - p0[k];
-                t.e2[k] = p2[k] - p0[k];
-            }
-            t.shade = gm.tri_offset + p.id;
-            t.flags = (gm.has_normal ? 1u : 0u) | (gm.has_uv ? 2u : 0u);
-            out->tris.push_back(t);
-        }
-        auto leaf_ref = [&](uint32_t first, uint32_t count) {
-            return ~static_cast<int32_t>(((tri_base + first) << 2) | (count - 1));
-        };
-        mesh_root[mi] = f4.emit(root, 1, leaf_ref);
-        out->blas_max_depth = std::max(out->blas_max_depth, f4.depth);
-        out->mesh_stack_need[mi] = blas_stack_need(out->nodes, mesh_root[mi]);
+    std::vector<Prim> prims = triangle_prims(mv, gm.tri_count);
+    const int leaf_knob = [] { const char* e = getenv("GBL_MAX_LEAF"); return e ? std::max(1, std::min(GBL_MAX_LEAF_TRIS, atoi(e))) : GBL_MAX_LEAF_TRIS; }();
+    Builder b(prims, leaf_knob, kBlasCap);
+    int root = b.build_parallel(prims.size());
+    Flat4 f4(b, out->nodes);
+    const uint32_t tri_base = static_cast<uint32_t>(out->tris.size());
+    for (const Prim& p : prims) {
+        const float *p0 = mv.p(p.id, 0), *p1 = mv.p(p.id, 1), *p2 = mv.p(p.id, 2);
+        DevTri t;
+        memset(&t, 0, sizeof(t));
+        for (int k = 0; k < 3; ++k) t.p0[k] = p0[k], t.e1[k] = p1[k] - p0[k], t.e2[k] = p2[k] - p0[k];
+        t.shade = gm.tri_offset + p.id;
+        t.flags = tri_flags(gm);
+        out->tris.push_back(t);
     }
-    out->blas_nodes = out->nodes.size();
-    out->mesh_lo.resize(3 * d->num_meshes);
-    out->mesh_hi.resize(3 * d->num_meshes);
-    for (uint32_t mi = 0; mi < d->num_meshes; ++mi)
-        for (int k = 0; k < 3; ++k) {
-            out->mesh_lo[3 * mi + k] = mesh_bounds[mi].lo[k];
-            out->mesh_hi[3 * mi + k] = mesh_bounds[mi].hi[k];
-        }
+    auto leaf_ref = [&](uint32_t first, uint32_t count) { return ~static_cast<int32_t>(((tri_base + first) << 2) | (count - 1)); };
+    out->mesh_root[mi] = f4.emit(root, 1, leaf_ref);
+    out->blas_max_depth = std::max(out->blas_max_depth, f4.depth);
+    out->mesh_stack_need[mi] = blas_stack_need(out->nodes, out->mesh_root[mi]);
+}
 
-    // ---- instances + TLAS
-    out->mesh_root = mesh_root;
-    out->tlas_base = static_cast<int32_t>(out->nodes.size());
-    out->tlas_capacity = std::max<uint32_t>(1u, d->num_instances);
-    std::vector<DevNode> tlas;
-    float sb_lo[3], sb_hi[3];
-    {
-        gbl_status ts = build_tlas(d->instances, d->num_instances, d->meshes, d->materials, out->mesh_lo.data(), out->mesh_hi.data(),
-                                   mesh_root.data(), out->tlas_base, &out->instances, &tlas, &out->tlas_root, &out->tlas_depth, sb_lo, sb_hi, err,
-                                   &out->instance_bounds);
-        if (ts != GBL_OK) return ts;
+// One mesh: its object bound, root reference and shading records; the tree itself unless the device builds it (kernels/lbvh.h
+// then makes the tree and the DevTri order)
+void pack_blas(const gbl_scene_desc& d, uint32_t mi, bool device_blas, PackedScene* out) {
+    const gbl_mesh& gm = d.meshes[mi];
+    Aabb bound;
+    if (gm.shape != GBL_SHAPE_MESH) {
+        // Sphere / Disk::getObjectBound (GoblinSphere.cpp:140-143, GoblinDisk.cpp:81-84); no BLAS: the
+        // instance's root is a marker reference and the traversal tests the shape analytically
+        const float r = gm.radius, z = gm.shape == GBL_SHAPE_SPHERE ? gm.radius : 0.0f;
+        float hi[3] = {r, r, z}, lo[3] = {-r, -r, -z};
+        bound.grow(hi);
+        bound.grow(lo);
+        out->mesh_root[mi] = gm.shape == GBL_SHAPE_SPHERE ? GBL_REF_SPHERE : GBL_REF_DISK;
+        out->extended = 1;
+    } else {
+        const MeshView mv = view_of(d, gm);
+        for (uint32_t v = 0; v < gm.vertex_count; ++v) bound.grow(mv.P + 3 * v);
+        for (uint32_t t = 0; t < gm.tri_count; ++t) {
+            DevTriShade& s = out->tri_shade[gm.tri_offset + t];
+            for (int k = 0; k < 3; ++k) s.v[k] = gm.vertex_offset + mv.I[3 * t + k];
+            s.flags = tri_flags(gm);
+        }
+        if (!device_blas) build_host_blas(gm, mv, mi, out);   // (a device build patches the root, 0 until then, after its build)
     }
+    store_bound(bound, &out->mesh_lo[3 * mi], &out->mesh_hi[3 * mi]);
+}
+
+// One BLAS per mesh, then the triangle bounds in the order of `tris` (what the kernels index with a hit's triangle; a device
+// build gathers them itself)
+void pack_meshes(const gbl_scene_desc& d, bool device_blas, PackedScene* out) {
+    out->tris.clear();
+    out->tri_shade.assign(d.num_triangles, DevTriShade());
+    out->blas_max_depth = 0;
+    out->mesh_stack_need.assign(d.num_meshes, 0);
+    out->mesh_root.assign(d.num_meshes, 0);
+    out->mesh_lo.resize(3 * d.num_meshes);
+    out->mesh_hi.resize(3 * d.num_meshes);
+    for (uint32_t mi = 0; mi < d.num_meshes; ++mi) pack_blas(d, mi, device_blas, out);
+    out->blas_nodes = out->nodes.size();
+    out->tri_bounds_leaf.resize(out->tris.size());
+    for (size_t i = 0; i < out->tris.size(); ++i) out->tri_bounds_leaf[i] = out->tri_bounds[out->tris[i].shade];
+}
+
+// The instance records and the TLAS behind the BLAS nodes; returns the scene bound: BVH::getAABB of the scene BVH, the union
+// of the instance boxes (GoblinBVH.cpp:46-50)
+gbl_status pack_instances(const gbl_scene_desc& d, PackedScene* out, Aabb* scene_bound, std::string* err) {
+    out->tlas_base = static_cast<int32_t>(out->nodes.size());
+    out->tlas_capacity = std::max<uint32_t>(1u, d.num_instances);
+    const TlasInput in = {d.instances,         d.num_instances,       d.meshes,     d.materials, out->mesh_lo.data(),
+                          out->mesh_hi.data(), out->mesh_root.data(), out->tlas_base};
+    TlasResult tlas;
+    const gbl_status st = build_tlas(in, &tlas, err);
+    if (st != GBL_OK) return st;
+    out->instances.swap(tlas.instances);
+    out->instance_bounds.swap(tlas.instance_bounds);
+    out->tlas_root = tlas.root;
+    out->tlas_depth = tlas.depth;
     for (const DevInstance& di : out->instances)
         if (di.is_mask) out->has_masks = out->extended = 1;
-    Aabb scene_bound;   // BVH::getAABB of the scene BVH: the union of the instance boxes (GoblinBVH.cpp:46-50)
-    scene_bound.grow(sb_lo);
-    scene_bound.grow(sb_hi);
-    out->nodes.insert(out->nodes.end(), tlas.begin(), tlas.end());
-    out->tlas_nodes = tlas.size();
+    scene_bound->grow(tlas.bound_lo);
+    scene_bound->grow(tlas.bound_hi);
+    out->nodes.insert(out->nodes.end(), tlas.nodes.begin(), tlas.nodes.end());
+    out->tlas_nodes = tlas.nodes.size();
     // room for any TLAS over the same instances (gbl_update_instances rebuilds it in place)
     out->nodes.resize(static_cast<size_t>(out->tlas_base) + out->tlas_capacity, DevNode());
     // (with device-built BLASes the caller fills mesh_stack_need from their depths and calls scene_stack_entries again)
-    out->stack_entries = scene_stack_entries(tlas, out->tlas_base, out->tlas_root, out->instances, out->mesh_stack_need);
+    out->stack_entries = scene_stack_entries(tlas.nodes, out->tlas_base, out->tlas_root, out->instances, out->mesh_stack_need);
+    return GBL_OK;
+}
 
-    // ---- materials
-    out->materials.resize(d->num_materials);
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const gbl_material& m = d->materials[i];
-        if (m.type > GBL_MAT_SUBSURFACE) {
-            *err = "unknown material type";
-            return GBL_ERR_INVALID;
-        }
-        if (m.type == GBL_MAT_MASK && (m.masked_material < 0 || static_cast<uint32_t>(m.masked_material) >= d->num_materials ||
-                                       d->materials[m.masked_material].type == GBL_MAT_MASK ||
-                                       d->materials[m.masked_material].type == GBL_MAT_SUBSURFACE)) {
-            *err = "mask material " + std::to_string(i) + " must wrap a non-mask, non-subsurface material of the scene";
-            return GBL_ERR_INVALID;
-        }
+// ------------------------------------------- materials, images and textures
+void pack_materials(const gbl_scene_desc& d, PackedScene* out) {
+    out->materials.resize(d.num_materials);
+    for (uint32_t i = 0; i < d.num_materials; ++i) {
+        const gbl_material& m = d.materials[i];
         DevMaterial& dm = out->materials[i];
         memset(&dm, 0, sizeof(dm));
         dm.type = m.type;
-        for (int k = 0; k < 3; ++k) {
-            dm.color[k] = m.color[k];
-            dm.color2[k] = m.color2[k];
-        }
+        for (int k = 0; k < 3; ++k) dm.color[k] = m.color[k], dm.color2[k] = m.color2[k];
         dm.index = m.index;
         dm.k = m.k;
         dm.exponent = m.exponent;
@@ -890,7 +958,7 @@ gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* er
         dm.masked = m.type == GBL_MAT_MASK ? m.masked_material : -1;
         dm.tex_color3 = -1;
         // Material::perturb -> BumpShaders::evaluate; MaskMaterial::perturb forwards to the wrapped material (GoblinMaterial.h:456-458)
-        const gbl_material& bump_of = m.type == GBL_MAT_MASK ? d->materials[m.masked_material] : m;
+        const gbl_material& bump_of = m.type == GBL_MAT_MASK ? d.materials[m.masked_material] : m;
         dm.tex_bump = bump_of.tex_bump;
         dm.tex_normal = bump_of.tex_normal;
         if (dm.tex_bump >= 0 || dm.tex_normal >= 0) dm.has_tex = 1u;
@@ -906,49 +974,27 @@ gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* er
             out->has_bssrdf = out->extended = 1;
         }
         if (m.type == GBL_MAT_MASK) {
-            const gbl_material& in = d->materials[m.masked_material];
+            const gbl_material& in = d.materials[m.masked_material];
             if (in.tex_color >= 0 || in.tex_color2 >= 0 || in.tex_exponent >= 0) dm.has_tex = 1u;
         }
-        for (int32_t t : {m.tex_color, m.tex_color2, m.tex_exponent, m.type == GBL_MAT_SUBSURFACE ? m.tex_color3 : -1, m.tex_bump, m.tex_normal}) {
-            if (t < 0) continue;
-            out->extended = 1;
-            int depth = texture_depth(d, t, 0);
-            if (depth < 0) {
-                *err = "material " + std::to_string(i) + " references a texture out of range (or a cyclic texture graph)";
-                return GBL_ERR_INVALID;
-            }
-            if (depth > GBL_TEX_MAX_DEPTH) {
-                *err = "material " + std::to_string(i) + ": texture graph deeper than " + std::to_string(GBL_TEX_MAX_DEPTH) +
-                       " levels below the material slot is outside the device path";
-                return GBL_ERR_UNSUPPORTED;
-            }
-        }
+        for (int32_t t : texture_slots(m))
+            if (t >= 0) out->extended = 1;
     }
+}
 
-    // ---- images: the pyramids arrive built (gbl_image); the device wants every level's offset
-    out->images.resize(d->num_images);
-    for (uint32_t i = 0; i < d->num_images; ++i) {
-        const gbl_image& gi = d->images[i];
+// The pyramids arrive built (gbl_image); the device wants every level's offset
+void pack_images(const gbl_scene_desc& d, PackedScene* out) {
+    out->images.resize(d.num_images);
+    for (uint32_t i = 0; i < d.num_images; ++i) {
+        const gbl_image& gi = d.images[i];
         DevImage& di = out->images[i];
         memset(&di, 0, sizeof(di));
-        if (gi.width == 0 || gi.height == 0 || (gi.width & (gi.width - 1)) || (gi.height & (gi.height - 1)) || (gi.channels != 1 && gi.channels != 4) ||
-            gi.levels == 0 || gi.levels > 18) {
-            *err = "image " + std::to_string(i) + ": sides must be powers of two, channels 1 or 4, at most 18 levels";
-            return GBL_ERR_INVALID;
-        }
-        di.width = gi.width;
-        di.height = gi.height;
-        di.levels = gi.levels;
-        di.channels = gi.channels;
+        di.width = gi.width, di.height = gi.height, di.levels = gi.levels, di.channels = gi.channels;
         di.offset = gi.texel_offset;
         uint64_t off = 0;
         for (uint32_t l = 0; l < gi.levels; ++l) {
             di.level_offset[l] = static_cast<uint32_t>(off);
-            off += static_cast<uint64_t>(std::max(1u, gi.width >> l)) * std::max(1u, gi.height >> l) * gi.channels;
-        }
-        if (gi.texel_offset + off > d->num_texels || off >= (1ull << 32)) {
-            *err = "image " + std::to_string(i) + ": texels out of range";
-            return GBL_ERR_INVALID;
+            off += level_texels(gi, l);
         }
     }
     // MIPMap<T>::initEWALut (GoblinTexture.cpp:262-271)
@@ -957,478 +1003,428 @@ gbl_status pack_scene(const gbl_scene_desc* d, PackedScene* out, std::string* er
         const float r2 = static_cast<float>(i) / static_cast<float>(128 - 1);
         out->ewa_lut[i] = expf(-2.0f * r2) - expf(-2.0f);
     }
+}
 
-    // ---- textures
-    out->textures.resize(d->num_textures);
-    for (uint32_t i = 0; i < d->num_textures; ++i) {
-        const gbl_texture& g = d->textures[i];
-        if (g.type > GBL_TEX_IMAGE || g.mapping > GBL_MAP_SPHERICAL) {
-            *err = "unknown texture or mapping type";
-            return GBL_ERR_INVALID;
-        }
-        if (g.type == GBL_TEX_IMAGE && (g.image < 0 || static_cast<uint32_t>(g.image) >= d->num_images || g.image_filter > GBL_IMAGE_FILTER_EWA ||
-                                        g.address > GBL_ADDRESS_BORDER || d->images[g.image].channels != (g.is_float ? 1u : 4u))) {
-            *err = "image texture " + std::to_string(i) + ": bad image index, filter, address mode or channel count";
-            return GBL_ERR_INVALID;
-        }
+void pack_textures(const gbl_scene_desc& d, PackedScene* out) {
+    out->textures.resize(d.num_textures);
+    for (uint32_t i = 0; i < d.num_textures; ++i) {
+        const gbl_texture& g = d.textures[i];
         DevTexture& t = out->textures[i];
         memset(&t, 0, sizeof(t));
         t.type = g.type;
         t.is_float = g.is_float;
         for (int k = 0; k < 3; ++k) t.value[k] = g.is_float ? g.value[0] : g.value[k];
-        t.child[0] = g.child[0];
-        t.child[1] = g.child[1];
+        t.child[0] = g.child[0], t.child[1] = g.child[1];
         t.mapping = g.mapping;
         t.filter = g.type == GBL_TEX_IMAGE ? g.image_filter : g.filter;
         t.image = g.type == GBL_TEX_IMAGE ? g.image : -1;
         t.address = g.address;
         t.max_aniso = g.max_anisotropy;
-        for (int k = 0; k < 2; ++k) {
-            t.uv_scale[k] = g.uv_scale[k];
-            t.uv_offset[k] = g.uv_offset[k];
-        }
+        for (int k = 0; k < 2; ++k) t.uv_scale[k] = g.uv_scale[k], t.uv_offset[k] = g.uv_offset[k];
         if ((g.type == GBL_TEX_CHECKERBOARD || g.type == GBL_TEX_IMAGE) && g.mapping == GBL_MAP_SPHERICAL) {
             Trs tt = compose(g.to_tex.position, g.to_tex.orientation, g.to_tex.scale);   // SphericalMapping::mToTex
             store3x4(tt.m, t.to_tex);
         }
     }
+}
 
-    // ---- lights, power distribution (Scene ctor, CDF1D::init)
-    out->lights.resize(d->num_lights);
+// -------------------------------------------------------------------- lights
+// CDF1D::init over f[0 .. n): the normalised cdf[0 .. n], returns the integral
+float cdf1d(const float* f, size_t n, std::vector<float>* cdf) {
+    const float dx = 1.0f / n;
+    cdf->assign(n + 1, 0.0f);
+    for (size_t k = 1; k < n + 1; ++k) (*cdf)[k] = (*cdf)[k - 1] + (f[k - 1] * dx);
+    const float integral = (*cdf)[n];
+    for (size_t k = 1; k < n + 1; ++k) (*cdf)[k] /= integral;
+    return integral;
+}
+
+// Scene::getBoundingSphere's radius: the full diagonal of the scene bound (GoblinBBox.h:51-54)
+float bounding_radius(const Aabb& b) {
+    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
+    return std::sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+float luminance(const float c[3]) { return 0.212671f * c[0] + 0.715160f * c[1] + 0.072169f * c[2]; }
+
+// Luminance of a light's power c * k1 * k2, each channel multiplied in that order
+float power_of(const float c[3], float k1, float k2 = 1.0f) {
+    const float p[3] = {c[0] * k1 * k2, c[1] * k1 * k2, c[2] * k1 * k2};
+    return luminance(p);
+}
+
+struct Quat { float w, x, y, z; };
+Quat qmul(const Quat& a, const Quat& b) {   // GoblinQuaternion.h:45-48
+    const float d3 = a.x * b.x + a.y * b.y + a.z * b.z;
+    Quat r;
+    r.w = a.w * b.w - d3;
+    r.x = a.w * b.x + b.w * a.x + (a.y * b.z - a.z * b.y);
+    r.y = a.w * b.y + b.w * a.y + (a.z * b.x - a.x * b.z);
+    r.z = a.w * b.z + b.w * a.z + (a.x * b.y - a.y * b.x);
+    return r;
+}
+Quat qnorm(const Quat& q) {   // normalize(Quaternion), GoblinQuaternion.cpp:94-100
+    const float inv = 1.0f / sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+    return Quat{q.w * inv, q.x * inv, q.y * inv, q.z * inv};
+}
+Quat axis_angle(int axis, float angle) {   // Quaternion(axis, angle), GoblinQuaternion.cpp:9-15 (unit axes x = 0, y = 1)
+    const float t = angle * 0.5f, st = sinf(t);
+    return Quat{cosf(t), axis == 0 ? 1.0f * st : 0.0f * st, axis == 1 ? 1.0f * st : 0.0f * st, 0.0f * st};
+}
+
+// Light::setOrientation (GoblinLight.cpp:66-76): direction -> basis -> matrix -> quaternion (w x y z)
+void orientation_of(const float dir[3], float q[4]) {
+    float xa[3], ya[3];
+    if (fabsf(dir[0]) > fabsf(dir[1])) {
+        float il = 1.0f / sqrtf(dir[0] * dir[0] + dir[2] * dir[2]);
+        xa[0] = -dir[2] * il; xa[1] = 0.0f; xa[2] = dir[0] * il;
+    } else {
+        float il = 1.0f / sqrtf(dir[1] * dir[1] + dir[2] * dir[2]);
+        xa[0] = 0.0f; xa[1] = -dir[2] * il; xa[2] = dir[1] * il;
+    }
+    ya[0] = dir[1] * xa[2] - dir[2] * xa[1];
+    ya[1] = dir[2] * xa[0] - dir[0] * xa[2];
+    ya[2] = dir[0] * xa[1] - dir[1] * xa[0];
+    float R[3][3] = {{xa[0], ya[0], dir[0]}, {xa[1], ya[1], dir[1]}, {xa[2], ya[2], dir[2]}};
+    float qv[4];   // x y z w
+    float trace = R[0][0] + R[1][1] + R[2][2];
+    if (trace > 0.0f) {
+        float s = std::sqrt(trace + 1.0f);
+        qv[3] = s * 0.5f;
+        float t = 0.5f / s;
+        qv[0] = (R[2][1] - R[1][2]) * t;
+        qv[1] = (R[0][2] - R[2][0]) * t;
+        qv[2] = (R[1][0] - R[0][1]) * t;
+    } else {
+        int a = 0;
+        if (R[1][1] > R[0][0]) a = 1;
+        if (R[2][2] > R[a][a]) a = 2;
+        int b2 = (a + 1) % 3, c2 = (b2 + 1) % 3;
+        float s = std::sqrt(R[a][a] - R[b2][b2] - R[c2][c2] + 1.0f);
+        qv[a] = s * 0.5f;
+        float t = s != 0.0f ? 0.5f / s : s;
+        qv[3] = (R[c2][b2] - R[b2][c2]) * t;
+        qv[b2] = (R[b2][a] + R[a][b2]) * t;
+        qv[c2] = (R[c2][a] + R[a][c2]) * t;
+    }
+    q[0] = qv[3]; q[1] = qv[0]; q[2] = qv[1]; q[3] = qv[2];
+}
+
+const float kOne[3] = {1.0f, 1.0f, 1.0f}, kZero[3] = {0.0f, 0.0f, 0.0f};
+
+// Spot and directional lights: the axis the light works with is the third column of the matrix of its orientation.  The
+// spot light's ctor normalises the direction, the directional light's does not (GoblinLight.cpp:136-143).
+float pack_aimed_light(const gbl_light& gl, const Aabb& scene_bound, PackedScene* out, DevLight* dl) {
+    const bool spot = gl.type == GBL_LIGHT_SPOT;
+    float dir[3] = {gl.direction[0], gl.direction[1], gl.direction[2]};
+    if (spot) {
+        float inv_len = 1.0f / std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
+        for (int k = 0; k < 3; ++k) dir[k] *= inv_len;
+    }
+    float q[4];
+    orientation_of(dir, q);
+    const Trs t = compose(spot ? gl.position : kZero, q, kOne);
+    for (int k = 0; k < 3; ++k) dl->axis[k] = t.m.v[k][0] * 0.0f + t.m.v[k][1] * 0.0f + t.m.v[k][2] * 1.0f;
+    if (spot) return power_of(dl->color, kTwoPi, 1.0f - 0.5f * (dl->cos_max + dl->cos_falloff));
+    // DirectionalLight::power (:203-210): radius^2 * PI * radiance over Scene::getBoundingSphere
+    out->extended = 1;
+    const float radius = bounding_radius(scene_bound);
+    return power_of(dl->color, radius * radius * kPi);
+}
+
+// A mesh light's triangles with the CDF1D over their areas; returns the sum of the areas
+float pack_light_tris(const gbl_scene_desc& d, const gbl_mesh& gm, PackedScene* out, DevLight* dl) {
+    const MeshView mv = view_of(d, gm);
+    dl->tri_first = static_cast<uint32_t>(out->light_tris.size());
+    dl->tri_count = gm.tri_count;
+    std::vector<float> areas(gm.tri_count), cdf;
+    float sum = 0.0f;
+    for (uint32_t k = 0; k < gm.tri_count; ++k) {
+        const float *p0 = mv.p(k, 0), *p1 = mv.p(k, 1), *p2 = mv.p(k, 2);
+        float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+        float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+        float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        areas[k] = 0.5f * std::sqrt(cx * cx + cy * cy + cz * cz);
+        sum += areas[k];
+    }
+    cdf1d(areas.data(), areas.size(), &cdf);
+    for (uint32_t k = 0; k < gm.tri_count; ++k) {
+        DevLightTri lt;
+        memset(&lt, 0, sizeof(lt));
+        for (int c = 0; c < 3; ++c) {
+            lt.p0[c] = mv.p(k, 0)[c], lt.p1[c] = mv.p(k, 1)[c], lt.p2[c] = mv.p(k, 2)[c];
+            lt.n0[c] = mv.n(k, 0)[c], lt.n1[c] = mv.n(k, 1)[c], lt.n2[c] = mv.n(k, 2)[c];
+        }
+        lt.area = areas[k];
+        lt.cdf_lo = cdf[k], lt.cdf_hi = cdf[k + 1];
+        lt.has_normal = gm.has_normal ? 1.0f : 0.0f;
+        out->light_tris.push_back(lt);
+    }
+    return sum;
+}
+
+// AreaLight over a mesh's triangles or, as a GeometrySet over one intersectable geometry (GoblinLight.cpp:289-303), a sphere / disk
+float pack_area_light(const gbl_scene_desc& d, const gbl_light& gl, PackedScene* out, DevLight* dl) {
+    const Trs t = compose(gl.to_world.position, gl.to_world.orientation, gl.to_world.scale);
+    store3x4(t.m, dl->m);
+    store3x4(t.inv, dl->inv);
+    const gbl_mesh& gm = d.meshes[gl.mesh];
+    if (gm.shape != GBL_SHAPE_MESH) {
+        out->extended = 1;
+        dl->shape = gm.shape, dl->radius = gm.radius;
+        const float a = gm.shape == GBL_SHAPE_SPHERE ? 4.0f * kPi * gm.radius * gm.radius : kPi * gm.radius * gm.radius;
+        dl->sum_area = 0.0f + a;   // the set's sum over its one geometry
+    } else {
+        dl->sum_area = pack_light_tris(d, gm, out, dl);
+    }
+    const float world_area = dl->sum_area * (gl.to_world.scale[0] * gl.to_world.scale[1]);
+    return power_of(dl->color, kPi, world_area);
+}
+
+// The environment map's texels, AddressRepeat
+struct IblTexels {
+    const DevImage& im;
+    const float* texels;
+    int width(uint32_t level) const { return static_cast<int>(std::max(1u, im.width >> level)); }
+    int height(uint32_t level) const { return static_cast<int>(std::max(1u, im.height >> level)); }
+    float at(uint32_t level, int s, int t, int c) const {
+        const int w = width(level), h = height(level);
+        s %= w; t %= h;
+        if (s < 0) s += w;
+        if (t < 0) t += h;
+        return texels[im.offset + im.level_offset[level] + (static_cast<size_t>(t) * w + s) * 4 + c];
+    }
+};
+
+// CDF1D::init as a block of the device's distribution table: func[n], cdf[n + 1], integral
+float append_cdf_block(const std::vector<float>& f, std::vector<float>* block) {
+    std::vector<float> cdf;
+    const float integral = cdf1d(f.data(), f.size(), &cdf);
+    block->insert(block->end(), f.begin(), f.end());
+    block->insert(block->end(), cdf.begin(), cdf.end());
+    block->push_back(integral);
+    return integral;
+}
+
+// The IBL's sampling distribution: luminance * sin(theta) of level max(0, maxLevel - 8), as a CDF2D (marginal block, then the rows')
+void pack_ibl_distribution(const IblTexels& tx, PackedScene* out, DevLight* dl) {
+    const uint32_t level = tx.im.levels > 9 ? tx.im.levels - 1 - 8 : 0;
+    const int dw = tx.width(level), dh = tx.height(level);
+    dl->dist_offset = static_cast<uint32_t>(out->ibl_dist.size());
+    dl->dist_w = static_cast<uint32_t>(dw), dl->dist_h = static_cast<uint32_t>(dh);
+    std::vector<float> rows_block, row_integrals, marginal_block;
+    for (int r = 0; r < dh; ++r) {
+        const float sin_theta = sinf((static_cast<float>(r) + 0.5f) / static_cast<float>(dh) * kPi);
+        std::vector<float> f(dw);
+        for (int c = 0; c < dw; ++c) {
+            const float rgb[3] = {tx.at(level, c, r, 0), tx.at(level, c, r, 1), tx.at(level, c, r, 2)};
+            f[c] = luminance(rgb) * sin_theta;
+        }
+        row_integrals.push_back(append_cdf_block(f, &rows_block));
+    }
+    append_cdf_block(row_integrals, &marginal_block);
+    out->ibl_dist.insert(out->ibl_dist.end(), marginal_block.begin(), marginal_block.end());
+    out->ibl_dist.insert(out->ibl_dist.end(), rows_block.begin(), rows_block.end());
+}
+
+// ImageBasedLight's constructor (GoblinLight.cpp:464-508)
+float pack_ibl_light(const gbl_scene_desc& d, const gbl_light& gl, const Aabb& scene_bound, PackedScene* out, DevLight* dl) {
+    out->extended = 1;
+    out->has_ibl = 1;
+    dl->image = gl.image;
+    // mToWorld.rotateX(-PI / 2); rotateY(-PI / 2); setOrientation(orientation * mToWorld.getOrientation())
+    Quat q = {1.0f, 0.0f, 0.0f, 0.0f};
+    q = qnorm(qmul(axis_angle(0, -0.5f * kPi), q));
+    q = qnorm(qmul(axis_angle(1, -0.5f * kPi), q));
+    q = qmul(Quat{gl.to_world.orientation[0], gl.to_world.orientation[1], gl.to_world.orientation[2], gl.to_world.orientation[3]}, q);
+    const float qq[4] = {q.w, q.x, q.y, q.z};
+    const Trs t = compose(kZero, qq, kOne);
+    store3x4(t.m, dl->m);
+    store3x4(t.inv, dl->inv);
+    const IblTexels tx = {out->images[gl.image], d.texels};
+    // mAverageRadiance = mRadiance->lookup(maxLevel, 0, 0): the bilinear lookup of the 1 x 1 level
+    const uint32_t max_level = tx.im.levels - 1;
+    const float s_res = 0.0f * tx.width(max_level) - 0.5f, t_res = 0.0f * tx.height(max_level) - 0.5f;
+    const int s0 = static_cast<int>(floorf(s_res)), t0 = static_cast<int>(floorf(t_res));
+    const float ds = s_res - static_cast<float>(s0), dt = t_res - static_cast<float>(t0);
+    float avg[3];
+    for (int c = 0; c < 3; ++c)
+        avg[c] = (1.0f - ds) * (1.0f - dt) * tx.at(max_level, s0, t0, c) + (ds) * (1.0f - dt) * tx.at(max_level, s0 + 1, t0, c) +
+                 (1.0f - ds) * (dt)*tx.at(max_level, s0, t0 + 1, c) + (ds) * (dt)*tx.at(max_level, s0 + 1, t0 + 1, c);
+    pack_ibl_distribution(tx, out, dl);
+    // ImageBasedLight::power (:606-613): mAverageRadiance * PI * (4 PI r^2) over the scene's bounding sphere
+    const float radius = bounding_radius(scene_bound);
+    return power_of(avg, kPi, 4.0f * kPi * radius * radius);
+}
+
+// One function per kind of light, each returning the light's power; then the power distribution (Scene ctor, CDF1D::init)
+void pack_lights(const gbl_scene_desc& d, const Aabb& scene_bound, PackedScene* out) {
+    out->lights.resize(d.num_lights);
     out->light_tris.clear();
-    std::vector<float> power(d->num_lights);
-    for (uint32_t i = 0; i < d->num_lights; ++i) {
-        const gbl_light& gl = d->lights[i];
+    std::vector<float> power(d.num_lights);
+    for (uint32_t i = 0; i < d.num_lights; ++i) {
+        const gbl_light& gl = d.lights[i];
         DevLight& dl = out->lights[i];
         memset(&dl, 0, sizeof(dl));
         dl.type = gl.type;
-        for (int k = 0; k < 3; ++k) {
-            dl.color[k] = gl.color[k];
-            dl.pos[k] = gl.position[k];
+        for (int k = 0; k < 3; ++k) dl.color[k] = gl.color[k], dl.pos[k] = gl.position[k];
+        dl.cos_max = gl.cos_theta_max, dl.cos_falloff = gl.cos_falloff_start;
+        switch (gl.type) {
+            case GBL_LIGHT_SPOT:
+            case GBL_LIGHT_DIRECTIONAL: power[i] = pack_aimed_light(gl, scene_bound, out, &dl); break;
+            case GBL_LIGHT_AREA: power[i] = pack_area_light(d, gl, out, &dl); break;
+            case GBL_LIGHT_IBL: power[i] = pack_ibl_light(d, gl, scene_bound, out, &dl); break;
+            default: power[i] = power_of(dl.color, 4.0f * kPi); break;   // GBL_LIGHT_POINT
         }
-        dl.cos_max = gl.cos_theta_max;
-        dl.cos_falloff = gl.cos_falloff_start;
-        float pr, pg, pb;
-        if (gl.type == GBL_LIGHT_SPOT || gl.type == GBL_LIGHT_DIRECTIONAL) {
-            // Light::setOrientation (GoblinLight.cpp:66-76): direction -> basis -> quaternion -> matrix; the axis
-            // the light works with is that matrix's third column.  The spot light's ctor normalises the direction,
-            // the directional light's does not (:136-143).
-            float dir[3] = {gl.direction[0], gl.direction[1], gl.direction[2]};
-            if (gl.type == GBL_LIGHT_SPOT) {
-                float inv_len = 1.0f / std::sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
-                for (int k = 0; k < 3; ++k) dir[k] *= inv_len;
-            }
-            float xa[3], ya[3];
-            if (fabsf(dir[0]) > fabsf(dir[1])) {
-                float il = 1.0f / sqrtf(dir[0] * dir[0] + dir[2] * dir[2]);
-                xa[0] = -dir[2] * il; xa[1] = 0.0f; xa[2] = dir[0] * il;
-            } else {
-                float il = 1.0f / sqrtf(dir[1] * dir[1] + dir[2] * dir[2]);
-                xa[0] = 0.0f; xa[1] = -dir[2] * il; xa[2] = dir[1] * il;
-            }
-            ya[0] = dir[1] * xa[2] - dir[2] * xa[1];
-            ya[1] = dir[2] * xa[0] - dir[0] * xa[2];
-            ya[2] = dir[0] * xa[1] - dir[1] * xa[0];
-            float R[3][3] = {{xa[0], ya[0], dir[0]}, {xa[1], ya[1], dir[1]}, {xa[2], ya[2], dir[2]}};
-            float qv[4];   // x y z w
-            float trace = R[0][0] + R[1][1] + R[2][2];
-            if (trace > 0.0f) {
-                float s = std::sqrt(trace + 1.0f);
-                qv[3] = s * 0.5f;
-                float t = 0.5f / s;
-                qv[0] = (R[2][1] - R[1][2]) * t;
-                qv[1] = (R[0][2] - R[2][0]) * t;
-                qv[2] = (R[1][0] - R[0][1]) * t;
-            } else {
-                int a = 0;
-                if (R[1][1] > R[0][0]) a = 1;
-                if (R[2][2] > R[a][a]) a = 2;
-                int b2 = (a + 1) % 3, c2 = (b2 + 1) % 3;
-                float s = std::sqrt(R[a][a] - R[b2][b2] - R[c2][c2] + 1.0f);
-                qv[a] = s * 0.5f;
-                float t = s != 0.0f ? 0.5f / s : s;
-                qv[3] = (R[c2][b2] - R[b2][c2]) * t;
-                qv[b2] = (R[b2][a] + R[a][b2]) * t;
-                qv[c2] = (R[c2][a] + R[a][c2]) * t;
-            }
-            float q[4] = {qv[3], qv[0], qv[1], qv[2]};
-            float one[3] = {1.0f, 1.0f, 1.0f}, zero[3] = {0.0f, 0.0f, 0.0f};
-            Trs t = compose(gl.type == GBL_LIGHT_SPOT ? gl.position : zero, q, one);
-            for (int k = 0; k < 3; ++k) dl.axis[k] = t.m.v[k][0] * 0.0f + t.m.v[k][1] * 0.0f + t.m.v[k][2] * 1.0f;
-            if (gl.type == GBL_LIGHT_SPOT) {
-                float solid = kTwoPi;
-                float f = (1.0f - 0.5f * (dl.cos_max + dl.cos_falloff));
-                pr = dl.color[0] * solid * f; pg = dl.color[1] * solid * f; pb = dl.color[2] * solid * f;
-            } else {
-                // DirectionalLight::power (:203-210): radius^2 * PI * radiance over Scene::getBoundingSphere, whose
-                // radius is the full diagonal of the scene bound (GoblinBBox.h:51-54)
-                out->extended = 1;
-                float dx = scene_bound.hi[0] - scene_bound.lo[0], dy = scene_bound.hi[1] - scene_bound.lo[1],
-                      dz = scene_bound.hi[2] - scene_bound.lo[2];
-                float radius = std::sqrt(dx * dx + dy * dy + dz * dz);
-                float a = radius * radius * kPi;
-                pr = a * dl.color[0]; pg = a * dl.color[1]; pb = a * dl.color[2];
-            }
-        } else if (gl.type == GBL_LIGHT_AREA && gl.mesh >= d->num_meshes) {
-            *err = "area light references a mesh out of range";
-            return GBL_ERR_INVALID;
-        } else if (gl.type == GBL_LIGHT_AREA && d->meshes[gl.mesh].shape != GBL_SHAPE_MESH) {
-            // GeometrySet over one intersectable geometry (GoblinLight.cpp:289-303)
-            out->extended = 1;
-            Trs t = compose(gl.to_world.position, gl.to_world.orientation, gl.to_world.scale);
-            store3x4(t.m, dl.m);
-            store3x4(t.inv, dl.inv);
-            const gbl_mesh& gm = d->meshes[gl.mesh];
-            dl.shape = gm.shape;
-            dl.radius = gm.radius;
-            float a = gm.shape == GBL_SHAPE_SPHERE ? 4.0f * kPi * gm.radius * gm.radius : kPi * gm.radius * gm.radius;
-            float sum = 0.0f;
-            sum += a;
-            dl.sum_area = sum;
-            dl.tri_first = dl.tri_count = 0;
-            float world_area = sum * (gl.to_world.scale[0] * gl.to_world.scale[1]);
-            pr = dl.color[0] * kPi * world_area; pg = dl.color[1] * kPi * world_area; pb = dl.color[2] * kPi * world_area;
-        } else if (gl.type == GBL_LIGHT_AREA) {
-            if (gl.mesh >= d->num_meshes) {
-                *err = "area light references a mesh out of range";
-                return GBL_ERR_INVALID;
-            }
-            Trs t = compose(gl.to_world.position, gl.to_world.orientation, gl.to_world.scale);
-            store3x4(t.m, dl.m);
-            store3x4(t.inv, dl.inv);
-            const gbl_mesh& gm = d->meshes[gl.mesh];
-            const float* P = d->positions + 3 * static_cast<size_t>(gm.vertex_offset);
-            const float* N = d->normals + 3 * static_cast<size_t>(gm.vertex_offset);
-            const uint32_t* I = d->indices + 3 * static_cast<size_t>(gm.tri_offset);
-            dl.tri_first = static_cast<uint32_t>(out->light_tris.size());
-            dl.tri_count = gm.tri_count;
-            std::vector<float> areas(gm.tri_count);
-            float sum = 0.0f;
-            for (uint32_t k = 0; k < gm.tri_count; ++k) {
-                const float* p0 = P + 3 * I[3 * k];
-                const float* p1 = P + 3 * I[3 * k + 1];
-                const float* p2 = P + 3 * I[3 * k + 2];
-                float e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-                float e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-                float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-                areas[k] = 0.5f * std::sqrt(cx * cx + cy * cy + cz * cz);
-                sum += areas[k];
-            }
-            dl.sum_area = sum;
-            // CDF1D over the triangle areas
-            float dx = 1.0f / gm.tri_count;
-            std::vector<float> cdf(gm.tri_count + 1, 0.0f);
-            for (uint32_t k = 1; k <= gm.tri_count; ++k) cdf[k] = cdf[k - 1] + (areas[k - 1] * dx);
-            float integral = cdf[gm.tri_count];
-            for (uint32_t k = 1; k <= gm.tri_count; ++k) cdf[k] /= integral;
-            for (uint32_t k = 0; k < gm.tri_count; ++k) {
-                DevLightTri lt;
-                memset(&lt, 0, sizeof(lt));
-                for (int c = 0; c < 3; ++c) {
-                    lt.p0[c] = P[3 * I[3 * k] + c];
-                    lt.p1[c] = P[3 * I[3 * k + 1] + c];
-                    lt.p2[c] = P[3 * I[3 * k + 2] + c];
-                    lt.n0[c] = N[3 * I[3 * k] + c];
-                    lt.n1[c] = N[3 * I[3 * k + 1] + c];
-                    lt.n2[c] = N[3 * I[3 * k + 2] + c];
-                }
-                lt.area = areas[k];
-                lt.cdf_lo = cdf[k];
-                lt.cdf_hi = cdf[k + 1];
-                lt.has_normal = gm.has_normal ? 1.0f : 0.0f;
-                out->light_tris.push_back(lt);
-            }
-            float world_area = sum * (gl.to_world.scale[0] * gl.to_world.scale[1]);
-            pr = dl.color[0] * kPi * world_area; pg = dl.color[1] * kPi * world_area; pb = dl.color[2] * kPi * world_area;
-        } else if (gl.type == GBL_LIGHT_IBL) {
-            // ImageBasedLight's constructor (GoblinLight.cpp:464-508)
-            if (gl.image < 0 || static_cast<uint32_t>(gl.image) >= d->num_images || d->images[gl.image].channels != 4) {
-                *err = "image based light " + std::to_string(i) + ": bad image index";
-                return GBL_ERR_INVALID;
-            }
-            out->extended = 1;
-            out->has_ibl = 1;
-            dl.image = gl.image;
-            // mToWorld.rotateX(-PI / 2); rotateY(-PI / 2); setOrientation(orientation * mToWorld.getOrientation())
-            struct Q { float w, x, y, z; };
-            auto qmul = [](const Q& a, const Q& b) {   // GoblinQuaternion.h:45-48
-                const float d3 = a.x * b.x + a.y * b.y + a.z * b.z;
-                Q r;
-                r.w = a.w * b.w - d3;
-                r.x = a.w * b.x + b.w * a.x + (a.y * b.z - a.z * b.y);
-                r.y = a.w * b.y + b.w * a.y + (a.z * b.x - a.x * b.z);
-                r.z = a.w * b.z + b.w * a.z + (a.x * b.y - a.y * b.x);
-                return r;
-            };
-            auto qnorm = [](const Q& q) {              // normalize(Quaternion), GoblinQuaternion.cpp:94-100
-                const float inv = 1.0f / sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-                Q r = {q.w * inv, q.x * inv, q.y * inv, q.z * inv};
-                return r;
-            };
-            auto axis_angle = [](int axis, float angle) {   // Quaternion(axis, angle), GoblinQuaternion.cpp:9-15 (unit axes)
-                const float t = angle * 0.5f, st = sinf(t);
-                Q r = {cosf(t), axis == 0 ? 1.0f * st : 0.0f * st, axis == 1 ? 1.0f * st : 0.0f * st, 0.0f * st};
-                return r;
-            };
-            Q q = {1.0f, 0.0f, 0.0f, 0.0f};
-            q = qnorm(qmul(axis_angle(0, -0.5f * kPi), q));
-            q = qnorm(qmul(axis_angle(1, -0.5f * kPi), q));
-            const Q given = {gl.to_world.orientation[0], gl.to_world.orientation[1], gl.to_world.orientation[2], gl.to_world.orientation[3]};
-            q = qmul(given, q);
-            const float qq[4] = {q.w, q.x, q.y, q.z}, one[3] = {1.0f, 1.0f, 1.0f}, zero[3] = {0.0f, 0.0f, 0.0f};
-            Trs t = compose(zero, qq, one);
-            store3x4(t.m, dl.m);
-            store3x4(t.inv, dl.inv);
-            const DevImage& im = out->images[gl.image];
-            auto texel = [&](uint32_t level, int s, int tt, int c) {   // AddressRepeat
-                const int w = static_cast<int>(std::max(1u, im.width >> level)), h = static_cast<int>(std::max(1u, im.height >> level));
-                s %= w; tt %= h;
-                if (s < 0) s += w;
-                if (tt < 0) tt += h;
-                return d->texels[im.offset + im.level_offset[level] + (static_cast<size_t>(tt) * w + s) * 4 + c];
-            };
-            // mAverageRadiance = mRadiance->lookup(maxLevel, 0, 0): the bilinear lookup of the 1 x 1 level
-            const uint32_t max_level = im.levels - 1;
-            float avg[3];
-            {
-                const int w = static_cast<int>(std::max(1u, im.width >> max_level)), h = static_cast<int>(std::max(1u, im.height >> max_level));
-                const float s_res = 0.0f * w - 0.5f, t_res = 0.0f * h - 0.5f;
-                const int s0 = static_cast<int>(floorf(s_res)), t0 = static_cast<int>(floorf(t_res));
-                const float ds = s_res - static_cast<float>(s0), dt = t_res - static_cast<float>(t0);
-                for (int c = 0; c < 3; ++c)
-                    avg[c] = (1.0f - ds) * (1.0f - dt) * texel(max_level, s0, t0, c) + (ds) * (1.0f - dt) * texel(max_level, s0 + 1, t0, c) +
-                             (1.0f - ds) * (dt)*texel(max_level, s0, t0 + 1, c) + (ds) * (dt)*texel(max_level, s0 + 1, t0 + 1, c);
-            }
-            // the sampling distribution: luminance * sin(theta) of level max(0, maxLevel - 8), as a CDF2D
-            const uint32_t dl_level = im.levels > 9 ? max_level - 8 : 0;
-            const int dw = static_cast<int>(std::max(1u, im.width >> dl_level)), dh = static_cast<int>(std::max(1u, im.height >> dl_level));
-            dl.dist_offset = static_cast<uint32_t>(out->ibl_dist.size());
-            dl.dist_w = static_cast<uint32_t>(dw);
-            dl.dist_h = static_cast<uint32_t>(dh);
-            auto cdf1d = [](const std::vector<float>& f, std::vector<float>* out_block) {   // CDF1D::init; block = func[n], cdf[n + 1], integral
-                const size_t n = f.size();
-                const float dx = 1.0f / n;
-                std::vector<float> cdf(n + 1, 0.0f);
-                for (size_t k = 1; k < n + 1; ++k) cdf[k] = cdf[k - 1] + (f[k - 1] * dx);
-                const float integral = cdf[n];
-                for (size_t k = 1; k < n + 1; ++k) cdf[k] /= integral;
-                out_block->insert(out_block->end(), f.begin(), f.end());
-                out_block->insert(out_block->end(), cdf.begin(), cdf.end());
-                out_block->push_back(integral);
-                return integral;
-            };
-            std::vector<float> rows_block, row_integrals;
-            for (int r = 0; r < dh; ++r) {
-                const float sin_theta = sinf((static_cast<float>(r) + 0.5f) / static_cast<float>(dh) * kPi);
-                std::vector<float> f(dw);
-                for (int c = 0; c < dw; ++c)
-                    f[c] = (0.212671f * texel(dl_level, c, r, 0) + 0.715160f * texel(dl_level, c, r, 1) + 0.072169f * texel(dl_level, c, r, 2)) * sin_theta;
-                row_integrals.push_back(cdf1d(f, &rows_block));
-            }
-            std::vector<float> marginal_block;
-            cdf1d(row_integrals, &marginal_block);
-            out->ibl_dist.insert(out->ibl_dist.end(), marginal_block.begin(), marginal_block.end());
-            out->ibl_dist.insert(out->ibl_dist.end(), rows_block.begin(), rows_block.end());
-            // ImageBasedLight::power (:606-613): mAverageRadiance * PI * (4 PI r^2) over the scene's bounding sphere
-            float dx = scene_bound.hi[0] - scene_bound.lo[0], dy = scene_bound.hi[1] - scene_bound.lo[1], dz = scene_bound.hi[2] - scene_bound.lo[2];
-            float radius = std::sqrt(dx * dx + dy * dy + dz * dz);
-            float a = 4.0f * kPi * radius * radius;
-            pr = avg[0] * kPi * a; pg = avg[1] * kPi * a; pb = avg[2] * kPi * a;
-        } else if (gl.type == GBL_LIGHT_POINT) {
-            float s = 4.0f * kPi;
-            pr = dl.color[0] * s; pg = dl.color[1] * s; pb = dl.color[2] * s;
-        } else {
-            *err = "unknown light type";
-            return GBL_ERR_INVALID;
-        }
-        power[i] = 0.212671f * pr + 0.715160f * pg + 0.072169f * pb;
         // WhittedRenderer::querySampleQuota: LightSampleIndex(quota, getSamplesNum()) -> roundToSquare slots
-        {
-            const int root = static_cast<int>(std::ceil(std::sqrt(static_cast<float>(gl.sample_num))));
-            dl.wh_n = static_cast<uint32_t>(root * root);
-            dl.wh_prefix = static_cast<uint32_t>(out->wh_slots);
-            out->wh_slots += static_cast<int32_t>(dl.wh_n);
-        }
+        const int root = static_cast<int>(std::ceil(std::sqrt(static_cast<float>(gl.sample_num))));
+        dl.wh_n = static_cast<uint32_t>(root * root);
+        dl.wh_prefix = static_cast<uint32_t>(out->wh_slots);
+        out->wh_slots += static_cast<int32_t>(dl.wh_n);
     }
-    out->light_cdf.assign(d->num_lights + 1, 0.0f);
-    out->light_pick_pdf.assign(std::max<uint32_t>(1, d->num_lights), 0.0f);
-    if (d->num_lights > 0) {
-        float dx = 1.0f / d->num_lights;
-        for (uint32_t i = 1; i <= d->num_lights; ++i) out->light_cdf[i] = out->light_cdf[i - 1] + (power[i - 1] * dx);
-        float integral = out->light_cdf[d->num_lights];
-        for (uint32_t i = 1; i <= d->num_lights; ++i) out->light_cdf[i] /= integral;
-        for (uint32_t i = 0; i < d->num_lights; ++i) out->light_pick_pdf[i] = (power[i] / integral) * dx;
-    }
+    out->light_cdf.assign(1, 0.0f);
+    out->light_pick_pdf.assign(std::max<uint32_t>(1, d.num_lights), 0.0f);
+    if (d.num_lights == 0) return;
+    const float integral = cdf1d(power.data(), power.size(), &out->light_cdf);
+    const float dx = 1.0f / d.num_lights;
+    for (uint32_t i = 0; i < d.num_lights; ++i) out->light_pick_pdf[i] = (power[i] / integral) * dx;
+}
 
-    // ---- participating medium
-    memset(&out->volume, 0, sizeof(out->volume));
-    if (d->volume.type == GBL_VOLUME_HOMOGENEOUS || d->volume.type == GBL_VOLUME_HETEROGENEOUS) {
-        DevVolume& v = out->volume;
-        v.on = 1u;
-        if (d->volume.type == GBL_VOLUME_HETEROGENEOUS) {
-            const gbl_volume& g = d->volume;
-            if (g.grid[0] <= 0 || g.grid[1] <= 0 || g.grid[2] <= 0 || (g.grid_channels != 1 && g.grid_channels != 3) || g.density == nullptr) {
-                *err = "heterogeneous volume: the density grid needs positive dimensions, 1 or 3 channels and its data";
-                return GBL_ERR_INVALID;
-            }
-            // the march loops of kernels/medium.h advance t by step_size: zero, negative, NaN or a step below the float spacing
-            // of t never terminates -- a spin on the reference's CPU, an unrecoverable hang on a GPU
-            if (!(g.step_size > 0.0f) || !std::isfinite(g.step_size)) {
-                *err = "heterogeneous volume: step_size must be a positive finite number";
-                return GBL_ERR_INVALID;
-            }
-            // the device indexes the grid with 32-bit ints
-            const uint64_t cells = static_cast<uint64_t>(g.grid[0]) * static_cast<uint64_t>(g.grid[1]);
-            if (cells > (1ull << 31) || cells * static_cast<uint64_t>(g.grid[2]) > (1ull << 31) ||
-                cells * static_cast<uint64_t>(g.grid[2]) * static_cast<uint64_t>(g.grid_channels) >= (1ull << 31)) {
-                *err = "heterogeneous volume: the density grid holds 2^31 values or more";
-                return GBL_ERR_INVALID;
-            }
-            v.hetero = 1u;
-            v.step = g.step_size;
-            v.nx = g.grid[0], v.ny = g.grid[1], v.nz = g.grid[2], v.nch = g.grid_channels;
-            out->vol_density.assign(g.density, g.density + static_cast<size_t>(v.nx) * v.ny * v.nz * v.nch);
-        }
-        for (int k = 0; k < 3; ++k) {
-            v.attenuation[k] = d->volume.attenuation[k];
-            v.scatter[k] = d->volume.attenuation[k] * d->volume.albedo[k];
-            v.emission[k] = d->volume.emission[k];
-            v.lo[k] = std::min(d->volume.box_min[k], d->volume.box_max[k]);   // BBox(p1, p2), GoblinBBox.h:20-23
-            v.hi[k] = std::max(d->volume.box_min[k], d->volume.box_max[k]);
-            v.bound_center[k] = 0.5f * (scene_bound.lo[k] + scene_bound.hi[k]);
-        }
-        for (int k = 0; k < 3; ++k) {
-            v.albedo[k] = d->volume.albedo[k];
-            v.normalize[k] = 1.0f / (v.hi[k] - v.lo[k]);
-        }
-        v.g = d->volume.g;
-        v.sample_num = d->volume.sample_num;
-        Trs t = compose(d->volume.to_world.position, d->volume.to_world.orientation, d->volume.to_world.scale);
-        store3x4(t.m, v.m);
-        store3x4(t.inv, v.inv);
-        if (v.hetero != 0u) {
-            // a march is at most (the region's longest world-space diagonal) / step_size points long: bounded at the 10^6 the
-            // stream sampler's draw budget assumes (api_render.hip medium_draws_per_sample) -- a step of 1e-12 is a hang, not a render
-            double diag = 0.0;
-            for (int sgn = 0; sgn < 4; ++sgn) {
-                const double e[3] = {double(v.hi[0] - v.lo[0]), (sgn & 1 ? -1.0 : 1.0) * double(v.hi[1] - v.lo[1]), (sgn & 2 ? -1.0 : 1.0) * double(v.hi[2] - v.lo[2])};
-                double w[3];
-                for (int r = 0; r < 3; ++r) w[r] = v.m[4 * r] * e[0] + v.m[4 * r + 1] * e[1] + v.m[4 * r + 2] * e[2];
-                diag = std::max(diag, std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]));
-            }
-            if (!(diag / double(v.step) <= 1.0e6)) {
-                *err = "heterogeneous volume: step_size is too small for the region (more than 10^6 steps across it)";
-                return GBL_ERR_INVALID;
-            }
-        }
-        const float dx = scene_bound.hi[0] - scene_bound.lo[0], dy = scene_bound.hi[1] - scene_bound.lo[1], dz = scene_bound.hi[2] - scene_bound.lo[2];
-        v.bound_radius = std::sqrt(dx * dx + dy * dy + dz * dz);
-        out->extended = 1;
-    } else if (d->volume.type != GBL_VOLUME_NONE) {
-        *err = "unknown volume type";
-        return GBL_ERR_INVALID;
+// ------------------------------------------------------ medium, film, hot prefix
+void pack_volume(const gbl_scene_desc& d, const Aabb& scene_bound, PackedScene* out) {
+    const gbl_volume& g = d.volume;
+    DevVolume& v = out->volume;
+    memset(&v, 0, sizeof(v));
+    if (g.type == GBL_VOLUME_NONE) return;
+    v.on = 1u;
+    if (g.type == GBL_VOLUME_HETEROGENEOUS) {
+        v.hetero = 1u;
+        v.step = g.step_size;
+        v.nx = g.grid[0], v.ny = g.grid[1], v.nz = g.grid[2], v.nch = g.grid_channels;
+        out->vol_density.assign(g.density, g.density + static_cast<size_t>(v.nx) * v.ny * v.nz * v.nch);
     }
-
-    // ---- camera
-    out->scene_extended = out->extended;
-    if (camera_extended(d->camera)) out->extended = 1;
-    pack_camera(d->camera, d->film, &out->camera);
-
-    // ---- film + filter table
-    const gbl_film& f = d->film;
-    if (f.xres <= 0 || f.yres <= 0) {
-        *err = "film resolution must be positive";
-        return GBL_ERR_INVALID;
+    const VolumeRegion region = region_of(g);
+    for (int k = 0; k < 3; ++k) {
+        v.attenuation[k] = g.attenuation[k], v.albedo[k] = g.albedo[k], v.emission[k] = g.emission[k];
+        v.scatter[k] = g.attenuation[k] * g.albedo[k];
+        v.lo[k] = region.lo[k], v.hi[k] = region.hi[k];
+        v.normalize[k] = 1.0f / (v.hi[k] - v.lo[k]);
+        v.bound_center[k] = 0.5f * (scene_bound.lo[k] + scene_bound.hi[k]);
     }
+    v.g = g.g;
+    v.sample_num = g.sample_num;
+    store3x4(region.to_world.m, v.m);
+    store3x4(region.to_world.inv, v.inv);
+    v.bound_radius = bounding_radius(scene_bound);
+    out->extended = 1;
+}
+
+void pack_film(const gbl_film& f, PackedScene* out) {
     DevFilm& df = out->film;
     memset(&df, 0, sizeof(df));
-    df.xres = f.xres;
-    df.yres = f.yres;
+    df.xres = f.xres, df.yres = f.yres;
     df.xstart = ceil_i(f.xres * f.crop[0]);
     df.xcount = std::max(1, ceil_i(f.xres * f.crop[1]) - df.xstart);
     df.ystart = ceil_i(f.yres * f.crop[2]);
     df.ycount = std::max(1, ceil_i(f.yres * f.crop[3]) - df.ystart);
-    df.wx = f.filter_width[0];
-    df.wy = f.filter_width[1];
+    df.wx = f.filter_width[0], df.wy = f.filter_width[1];
     df.window[0] = floor_i(df.xstart + 0.5f - df.wx);
     df.window[1] = floor_i(df.xstart + 0.5f + df.xcount + df.wx);
     df.window[2] = floor_i(df.ystart + 0.5f - df.wy);
     df.window[3] = floor_i(df.ystart + 0.5f + df.ycount + df.wy);
-    df.halo = ceil_i(std::max(df.wx, df.wy) + 0.5f);
-    if (!(df.wx > 0.0f) || !(df.wy > 0.0f) || df.halo > GBL_MAX_FILTER_HALO) {
-        *err = "filter width must be in (0, " + std::to_string(GBL_MAX_FILTER_HALO - 0.5f) + "] pixels";
-        return GBL_ERR_UNSUPPORTED;
-    }
-    Filter flt;
-    flt.type = f.filter_type;
-    flt.wx = df.wx; flt.wy = df.wy;
-    flt.alpha = f.gaussian_falloff;
-    flt.ex = expf(-flt.alpha * flt.wx * flt.wx);
-    flt.ey = expf(-flt.alpha * flt.wy * flt.wy);
-    flt.b = f.mitchell_b; flt.c = f.mitchell_c;
+    df.halo = filter_halo(f);
+    const float alpha = f.gaussian_falloff;
+    const Filter flt = {f.filter_type, df.wx, df.wy, alpha, expf(-alpha * df.wx * df.wx), expf(-alpha * df.wy * df.wy), f.mitchell_b, f.mitchell_c};
     float norm = flt.norm();
     float dxs = flt.wx / 16, dys = flt.wy / 16;
     for (int y = 0; y < 16; ++y)
         for (int x = 0; x < 16; ++x) out->filter_table[16 * y + x] = flt.eval(x * dxs, y * dys) / norm;
-    // the triangle bounds in the order of `tris` (what the kernels index with a hit's triangle); a device build gathers them itself
-    out->tri_bounds_leaf.resize(out->tris.size());
-    for (size_t i = 0; i < out->tris.size(); ++i) out->tri_bounds_leaf[i] = out->tri_bounds[out->tris[i].shade];
-    // ---- hot prefix: the nodes every ray starts with, once more, at indices [0, hot_nodes) in breadth-first order from the
-    // TLAS root through the instances' BLAS roots.  The lean kernels keep as many of them as their LDS has room for beside
-    // the traversal stacks (trace.h HotNodes): a reference below hot_nodes is served from LDS, anything else from memory.  The
-    // originals stay where they were (unreferenced from now on: at most GBL_HOT_NODES_MAX * 64 bytes); every interior reference
-    // -- child slots, instance roots, mesh roots, the TLAS root -- is rewritten to `hot index` or `old index + hot_nodes`, and
-    // tlas_base moves with the rest, so gbl_update_instances rebuilds the TLAS in the ordinary region and the BLAS part of the
-    // prefix stays valid.  (Host-built trees only: the device builder writes its nodes on the device.)
-    out->hot_nodes = 0;
-    if (!device_blas && !out->nodes.empty() && out->instances.size() > 0) {
-        uint32_t want = GBL_HOT_NODES_MAX;
-        if (const char* e = getenv("GBL_HOT_NODES")) want = static_cast<uint32_t>(std::max(0, std::min(4096, atoi(e))));
-        auto interior = [&](int32_t r) { return r >= 0 && static_cast<uint32_t>(r) < static_cast<uint32_t>(GBL_REF_NONE); };
-        std::vector<int32_t> order;          // old indices in breadth-first order
-        std::vector<int32_t> hot_of(out->nodes.size(), -1);
-        auto visit = [&](int32_t r) {
-            if (interior(r) && static_cast<size_t>(r) < out->nodes.size() && hot_of[r] < 0 && order.size() < want) {
-                hot_of[r] = static_cast<int32_t>(order.size());
-                order.push_back(r);
-            }
-        };
-        visit(out->tlas_root);
-        for (size_t head = 0; head < order.size() && order.size() < want; ++head) {
-            const DevNode& nd = out->nodes[order[head]];
-            for (int k = 0; k < 4; ++k) {
-                const int32_t c = nd.child[k];
-                if (interior(c)) {
-                    visit(c);
-                } else if (c < 0 && order[head] >= out->tlas_base) {   // a TLAS leaf: on into the instance's BLAS
-                    const uint32_t inst = (~static_cast<uint32_t>(c)) >> 2;
-                    if (inst < out->instances.size() && out->instances[inst].shape == 0u) visit(out->instances[inst].root);
-                }
-            }
+}
+
+bool interior_ref(int32_t r) { return r >= 0 && static_cast<uint32_t>(r) < static_cast<uint32_t>(GBL_REF_NONE); }
+
+// Hot prefix: the nodes every ray starts with, once more, at indices [0, hot_nodes) in breadth-first order.  The lean kernels
+// keep as many of them as their LDS has room for beside the traversal stacks (trace.h HotNodes): a reference below hot_nodes is
+// served from LDS, anything else from memory.  The originals stay where they were (unreferenced from now on: at most
+// GBL_HOT_NODES_MAX * 64 bytes); every interior reference -- child slots, instance roots, mesh roots, the TLAS root -- is
+// rewritten to `hot index` or `old index + hot_nodes`, and tlas_base moves with the rest, so gbl_update_instances rebuilds the
+// TLAS in the ordinary region and the BLAS part of the prefix stays valid.  (Host-built trees only: the device builder writes
+// its nodes on the device.)
+void hot_prefix(const gbl_scene_desc& d, PackedScene* out) {
+    if (out->nodes.empty() || out->instances.empty()) return;
+    uint32_t want = GBL_HOT_NODES_MAX;
+    if (const char* e = getenv("GBL_HOT_NODES")) want = static_cast<uint32_t>(std::max(0, std::min(4096, atoi(e))));
+    const PackedScene& s = *out;
+    std::vector<int32_t> order;          // old indices in breadth-first order: from the TLAS root through the instances' BLAS roots
+    std::vector<int32_t> hot_of(s.nodes.size(), -1);
+    auto visit = [&](int32_t r) {
+        if (interior_ref(r) && static_cast<size_t>(r) < s.nodes.size() && hot_of[r] < 0 && order.size() < want) {
+            hot_of[r] = static_cast<int32_t>(order.size());
+            order.push_back(r);
         }
-        if (interior(out->tlas_root) == false)   // a one-instance scene: the TLAS "root" is the instance's leaf reference itself
-            for (const DevInstance& di : out->instances)
-                if (di.shape == 0u) visit(di.root);
-        for (size_t head = 0; head < order.size() && order.size() < want; ++head)
-            for (int k = 0; k < 4; ++k) visit(out->nodes[order[head]].child[k]);
-        const int32_t H = static_cast<int32_t>(order.size());
-        if (H > 0) {
-            auto remap = [&](int32_t r) { return !interior(r) ? r : (hot_of[r] >= 0 ? hot_of[r] : r + H); };
-            std::vector<DevNode> moved;
-            moved.reserve(out->nodes.size() + H);
-            for (int32_t i = 0; i < H; ++i) moved.push_back(out->nodes[order[i]]);
-            moved.insert(moved.end(), out->nodes.begin(), out->nodes.end());
-            for (DevNode& nd : moved)
-                for (int k = 0; k < 4; ++k) nd.child[k] = remap(nd.child[k]);
-            out->nodes.swap(moved);
-            for (DevInstance& di : out->instances)
-                if (di.shape == 0u) di.root = remap(di.root);
-            for (uint32_t mi = 0; mi < d->num_meshes; ++mi)
-                if (d->meshes[mi].shape == GBL_SHAPE_MESH) out->mesh_root[mi] = remap(out->mesh_root[mi]);
-            out->tlas_root = remap(out->tlas_root);
-            out->tlas_base += H;
-            out->hot_nodes = static_cast<uint32_t>(H);
+    };
+    visit(s.tlas_root);
+    for (size_t head = 0; head < order.size() && order.size() < want; ++head) {
+        const DevNode& nd = s.nodes[order[head]];
+        for (int k = 0; k < 4; ++k) {
+            const int32_t c = nd.child[k];
+            if (interior_ref(c)) {
+                visit(c);
+            } else if (c < 0 && order[head] >= s.tlas_base) {   // a TLAS leaf: on into the instance's BLAS
+                const uint32_t inst = (~static_cast<uint32_t>(c)) >> 2;
+                if (inst < s.instances.size() && s.instances[inst].shape == 0u) visit(s.instances[inst].root);
+            }
         }
     }
+    if (!interior_ref(s.tlas_root))   // a one-instance scene: the TLAS "root" is the instance's leaf reference itself
+        for (const DevInstance& di : s.instances)
+            if (di.shape == 0u) visit(di.root);
+    for (size_t head = 0; head < order.size() && order.size() < want; ++head)
+        for (int k = 0; k < 4; ++k) visit(s.nodes[order[head]].child[k]);
+    const int32_t H = static_cast<int32_t>(order.size());
+    if (H == 0) return;
+    auto remap = [&](int32_t r) { return !interior_ref(r) ? r : (hot_of[r] >= 0 ? hot_of[r] : r + H); };
+    std::vector<DevNode> moved;
+    moved.reserve(out->nodes.size() + H);
+    for (int32_t i = 0; i < H; ++i) moved.push_back(out->nodes[order[i]]);
+    moved.insert(moved.end(), out->nodes.begin(), out->nodes.end());
+    for (DevNode& nd : moved)
+        for (int k = 0; k < 4; ++k) nd.child[k] = remap(nd.child[k]);
+    out->nodes.swap(moved);
+    for (DevInstance& di : out->instances)
+        if (di.shape == 0u) di.root = remap(di.root);
+    for (uint32_t mi = 0; mi < d.num_meshes; ++mi)
+        if (d.meshes[mi].shape == GBL_SHAPE_MESH) out->mesh_root[mi] = remap(out->mesh_root[mi]);
+    out->tlas_root = remap(out->tlas_root);
+    out->tlas_base += H;
+    out->hot_nodes = static_cast<uint32_t>(H);
+}
+
+}  // namespace
+
+// Validate, then pack: every refusal comes from validate_desc, before any table is built; of the packers only the TLAS step
+// returns a status (build_tlas keeps its check for gbl_update_instances) and after validation it cannot fail.
+gbl_status pack_scene(const gbl_scene_desc* desc, PackedScene* out, std::string* err, bool device_blas) {
+    const gbl_status valid = validate_desc(desc, err);
+    if (valid != GBL_OK) return valid;
+    const gbl_scene_desc& d = *desc;
+    out->extended = 0;   // the scene's part first; the camera's is added below
+    pack_attributes(d, out);
+    pack_tri_order_and_bounds(d, out);
+    pack_meshes(d, device_blas, out);
+    Aabb scene_bound;
+    const gbl_status st = pack_instances(d, out, &scene_bound, err);
+    if (st != GBL_OK) return st;
+    pack_materials(d, out);
+    pack_images(d, out);
+    pack_textures(d, out);
+    pack_lights(d, scene_bound, out);
+    pack_volume(d, scene_bound, out);
+    out->scene_extended = out->extended;
+    if (camera_extended(d.camera)) out->extended = 1;
+    pack_camera(d.camera, d.film, &out->camera);
+    pack_film(d.film, out);
+    out->hot_nodes = 0;
+    if (!device_blas) hot_prefix(d, out);
     return GBL_OK;
 }

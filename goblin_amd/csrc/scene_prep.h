@@ -46,7 +46,7 @@ struct PackedScene {
     DevFilm film;
 };
 
-// Returns GBL_OK or an error with *err set.
+// Returns GBL_OK or an error with *err set; every refusal is made before anything is written to *out.
 // device_blas: leave the triangle BLASes to the device builder (kernels/lbvh.h): `nodes` then holds the TLAS only
 // (at indices 0..), `tris` stays empty, mesh instances get root = 0 (patched after the device build) and
 // `mesh_lo/hi` carry the object bounds the Morton codes are scaled by.
@@ -58,11 +58,26 @@ void pack_camera(const gbl_camera& camera, const gbl_film& film, DevCamera* out)
 // The camera's part of DevScene::extended: a thin lens or an orthographic camera needs the EXT kernels
 bool camera_extended(const gbl_camera& camera);
 
-// The instance records and the TLAS over them (also used by gbl_update_instances to rebuild after transform edits).
-gbl_status build_tlas(const gbl_instance* inst, uint32_t n, const gbl_mesh* meshes, const gbl_material* materials, const float* mesh_lo,
-                      const float* mesh_hi, const int32_t* mesh_root, int32_t tlas_base, std::vector<DevInstance>* out_inst,
-                      std::vector<DevNode>* out_nodes, int32_t* tlas_root, int* tlas_depth, float sb_lo[3], float sb_hi[3], std::string* err,
-                      std::vector<DevInstanceBound>* bounds_out = nullptr);
+// The instance records and the TLAS over them (pack_scene; gbl_update_instances rebuilds with it after transform edits).
+struct TlasInput {
+    const gbl_instance* instances;
+    uint32_t count;
+    const gbl_mesh* meshes;
+    const gbl_material* materials;
+    const float *mesh_lo, *mesh_hi;   // 3 per mesh: object bounds
+    const int32_t* mesh_root;         // per mesh: BLAS root reference
+    int32_t tlas_base;                // device index of TLAS node 0
+};
+struct TlasResult {
+    std::vector<DevInstance> instances;
+    std::vector<DevNode> nodes;
+    std::vector<DevInstanceBound> instance_bounds;
+    int32_t root = 0;
+    int depth = 0;
+    float bound_lo[3], bound_hi[3];   // the scene bound: the union of the instance boxes
+};
+// Refuses (GBL_ERR_INVALID, *err set, *out unspecified) an instance whose transform the reference cannot invert.
+gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err);
 
 // Traversal stack entries a scene needs (kernels/trace.h): exit marker + the worst root-to-leaf sum over the TLAS nodes
 // (tlas[0..] are the nodes at absolute indices tlas_base + i) of (children - 1), + per instance its sentinel and what its

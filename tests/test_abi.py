@@ -97,6 +97,201 @@ def test_degenerate_march_steps_are_rejected_not_hung():
     assert b"2^31" in _abi.hip_lib().gbl_last_error(None)
 
 
+def _own(desc, field, n, extra=0):
+    """Give a description copy its own array behind `field` (its n elements and `extra` zeroed ones), so that a case can edit it."""
+    ptr = getattr(desc, field)
+    arr = (ptr._type_ * max(1, n + extra))()
+    C.memmove(arr, ptr, n * C.sizeof(ptr._type_))
+    setattr(desc, field, C.cast(arr, type(ptr)))
+    desc.__dict__.setdefault("_arrays", []).append(arr)
+    return arr
+
+
+def _first(items, n, pred):
+    return next(i for i in range(n) if pred(items[i]))
+
+
+def _bad_instance(field):
+    def edit(d):
+        limit = {"mesh": d.num_meshes, "material": d.num_materials, "area_light": d.num_lights}[field]
+        setattr(_own(d, "instances", d.num_instances)[0], field, limit)
+    return edit
+
+
+def _mesh_edit(**fields):
+    def edit(d):
+        m = _own(d, "meshes", d.num_meshes)[_first(d.meshes, d.num_meshes, lambda m: m.shape == _abi.GBL_SHAPE_MESH)]
+        for k, v in fields.items():
+            setattr(m, k, v)
+    return edit
+
+
+def _bad_vertex_index(d):
+    m = d.meshes[_first(d.meshes, d.num_meshes, lambda m: m.shape == _abi.GBL_SHAPE_MESH)]
+    _own(d, "indices", 3 * d.num_triangles)[3 * m.tri_offset + 1] = m.vertex_count
+
+
+def _degenerate_uv(d):
+    m = d.meshes[_first(d.meshes, d.num_meshes, lambda m: m.shape == _abi.GBL_SHAPE_MESH and m.has_uv)]
+    uv = _own(d, "uvs", 2 * d.num_vertices)
+    for v in range(m.vertex_count):   # every vertex of the mesh at one texture coordinate
+        uv[2 * (m.vertex_offset + v)], uv[2 * (m.vertex_offset + v) + 1] = 0.25, 0.75
+
+
+def _flat_instance(d):
+    _own(d, "instances", d.num_instances)[0].to_world.scale[1] = 0.0
+
+
+def _material_edit(**fields):
+    def edit(d):
+        m = _own(d, "materials", d.num_materials)[0]
+        for k, v in fields.items():
+            setattr(m, k, v(d) if callable(v) else v)
+    return edit
+
+
+def _mask_of_a_mask(d):
+    i = _first(d.materials, d.num_materials, lambda m: m.type == _abi.GBL_MAT_MASK)
+    _own(d, "materials", d.num_materials)[i].masked_material = i
+
+
+def _texture_chain(levels, cyclic=False):
+    """Material 0's colour slot gets a chain of `levels` scale textures over a constant (or over itself), appended to the scene's."""
+    def edit(d):
+        n = d.num_textures
+        tex = _own(d, "textures", n, levels + 1)
+        for k in range(levels):
+            tex[n + k].type = _abi.GBL_TEX_SCALE
+            nxt = n if (cyclic and k == levels - 1) else n + k + 1
+            tex[n + k].child[0], tex[n + k].child[1] = nxt, n + levels
+        tex[n + levels].type = _abi.GBL_TEX_CONSTANT
+        d.num_textures = n + levels + 1
+        _own(d, "materials", d.num_materials)[0].tex_color = n
+    return edit
+
+
+def _image_edit(**fields):
+    def edit(d):
+        for k, v in fields.items():
+            setattr(_own(d, "images", d.num_images)[0], k, v(d) if callable(v) else v)
+    return edit
+
+
+def _image_texture_edit(**fields):
+    def edit(d):
+        t = _own(d, "textures", d.num_textures)[_first(d.textures, d.num_textures, lambda t: t.type == _abi.GBL_TEX_IMAGE)]
+        for k, v in fields.items():
+            setattr(t, k, v)
+    return edit
+
+
+def _light_edit(kind, **fields):
+    def edit(d):
+        lt = _own(d, "lights", d.num_lights)[_first(d.lights, d.num_lights, lambda lt: kind is None or lt.type == kind)]
+        for k, v in fields.items():
+            setattr(lt, k, v(d) if callable(v) else v)
+    return edit
+
+
+def _volume_edit(**fields):
+    def edit(d):
+        for k, v in fields.items():
+            if k == "grid":
+                d.volume.grid[0], d.volume.grid[1] = v
+            else:
+                setattr(d.volume, k, v)
+    return edit
+
+
+def _film_edit(xres=None, width=None):
+    def edit(d):
+        if xres is not None:
+            d.film.xres = xres
+        if width is not None:
+            d.film.filter_width[0] = width
+    return edit
+
+
+def _camera_type(d):
+    d.camera.type = 7
+
+
+def _abi_version(d):
+    d.abi_version = 99
+
+
+def _both(*edits):
+    def edit(d):
+        for e in edits:
+            e(d)
+    return edit
+
+
+_INV, _UNS = _abi.GBL_ERR_INVALID, _abi.GBL_ERR_UNSUPPORTED
+# (id, scene, edit of a copy of its description, status, part of the message), in the order pack_scene refuses them
+REFUSALS = [
+    ("abi_version", "shapes", _abi_version, _INV, "wrong abi_version"),
+    ("camera_type", "shapes", _camera_type, _INV, "unknown camera type"),
+    ("instance_mesh", "shapes", _bad_instance("mesh"), _INV, "instance 0 references a mesh/material/light out of range"),
+    ("instance_material", "shapes", _bad_instance("material"), _INV, "instance 0 references a mesh/material/light out of range"),
+    ("instance_light", "shapes", _bad_instance("area_light"), _INV, "instance 0 references a mesh/material/light out of range"),
+    ("mesh_shape", "shapes", _mesh_edit(shape=9), _INV, "has an unknown shape"),
+    ("mesh_empty", "shapes", _mesh_edit(tri_count=0), _INV, "is empty or out of range"),
+    ("mesh_vertex_range", "shapes", _mesh_edit(vertex_offset=1 << 30), _INV, "is empty or out of range"),
+    ("mesh_vertex_index", "shapes", _bad_vertex_index, _INV, "has a vertex index out of range"),
+    ("mesh_degenerate_uv", "imagetex", _degenerate_uv, _UNS, "triangle 0 has degenerate texture coordinates"),
+    ("instance_not_invertible", "shapes", _flat_instance, _INV, "instance 0: |det(toWorld)| < 1e-5"),
+    ("material_type", "shapes", _material_edit(type=99), _INV, "unknown material type"),
+    ("mask_of_a_mask", "masked", _mask_of_a_mask, _INV, "must wrap a non-mask, non-subsurface material"),
+    ("mask_of_subsurface", "subsurface", _material_edit(type=_abi.GBL_MAT_MASK, masked_material=lambda d: _first(
+        d.materials, d.num_materials, lambda m: m.type == _abi.GBL_MAT_SUBSURFACE)), _INV, "must wrap a non-mask, non-subsurface material"),
+    ("texture_out_of_range", "shapes", _material_edit(tex_color=lambda d: d.num_textures), _INV, "material 0 references a texture out of range"),
+    ("texture_cycle", "shapes", _texture_chain(2, cyclic=True), _INV, "material 0 references a texture out of range (or a cyclic texture graph)"),
+    ("texture_too_deep", "shapes", _texture_chain(3), _UNS, "material 0: texture graph deeper than 2 levels"),
+    ("image_shape", "imagetex", _image_edit(width=3), _INV, "image 0: sides must be powers of two"),
+    ("image_levels", "imagetex", _image_edit(levels=19), _INV, "image 0: sides must be powers of two"),
+    ("image_texels", "imagetex", _image_edit(texel_offset=lambda d: d.num_texels), _INV, "image 0: texels out of range"),
+    ("texture_mapping", "imagetex", _image_texture_edit(mapping=9), _INV, "unknown texture or mapping type"),
+    ("image_texture_index", "imagetex", _image_texture_edit(image=-1), _INV, ": bad image index, filter, address mode or channel count"),
+    ("image_texture_filter", "imagetex", _image_texture_edit(image_filter=9), _INV, ": bad image index, filter, address mode or channel count"),
+    ("image_texture_address", "imagetex", _image_texture_edit(address=9), _INV, ": bad image index, filter, address mode or channel count"),
+    ("image_texture_channels", "imagetex", _image_texture_edit(is_float=1), _INV, ": bad image index, filter, address mode or channel count"),
+    ("area_light_mesh", "shapes", _light_edit(_abi.GBL_LIGHT_AREA, mesh=lambda d: d.num_meshes), _INV, "area light references a mesh out of range"),
+    ("ibl_image", "ibl", _light_edit(_abi.GBL_LIGHT_IBL, image=-1), _INV, "image based light 0: bad image index"),
+    ("light_type", "shapes", _light_edit(None, type=99), _INV, "unknown light type"),
+    ("volume_grid", "hetero", _volume_edit(grid_channels=2), _INV, "the density grid needs positive dimensions, 1 or 3 channels and its data"),
+    ("volume_step", "hetero", _volume_edit(step_size=0.0), _INV, "step_size must be a positive finite number"),
+    ("volume_cells", "hetero", _volume_edit(grid=(1 << 16, 1 << 16)), _INV, "holds 2^31 values or more"),
+    ("volume_steps", "hetero", _volume_edit(step_size=1e-12), _INV, "more than 10^6 steps across it"),
+    ("volume_type", "hetero", _volume_edit(type=9), _INV, "unknown volume type"),
+    ("film_resolution", "shapes", _film_edit(xres=0), _INV, "film resolution must be positive"),
+    ("filter_width", "shapes", _film_edit(width=9.0), _UNS, "filter width must be in (0, 5.5"),
+    # two faults: the earlier section's message wins
+    ("material_before_film", "shapes", _both(_film_edit(width=9.0), _material_edit(type=99)), _INV, "unknown material type"),
+    ("instance_before_light", "shapes", _both(_light_edit(None, type=99), _flat_instance), _INV, "instance 0: |det(toWorld)| < 1e-5"),
+    ("image_before_volume", "imagetex", _both(_volume_edit(type=9), _image_edit(width=3)), _INV, "image 0: sides must be powers of two"),
+]
+_refusal_scenes = {}
+
+
+@pytest.mark.parametrize("name,scene_name,edit,status,message", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_every_refusal_of_pack_scene_by_status_and_text(name, scene_name, edit, status, message):
+    """gbl_create packs the description before it looks for a device, so every refusal of pack_scene comes back with its own
+    status and message with or without a GPU.  One case per refusal, plus three descriptions with two faults that pin the order
+    the sections are checked in (description, camera, instance references, meshes, instance transforms, materials, images,
+    textures, lights, medium, film)."""
+    from goblin_amd import scene as gs
+    if scene_name not in _refusal_scenes:
+        _refusal_scenes[scene_name] = gs.load_scene(scene_name, gs.config_overrides(resolution=(16, 16), spp=1, depth=2))
+    desc = _abi.gbl_scene_desc.from_buffer_copy(_refusal_scenes[scene_name].desc)
+    edit(desc)
+    h = C.c_void_p()
+    got = _abi.hip_lib().gbl_create(C.byref(desc), 0, C.byref(h))
+    text = _abi.hip_lib().gbl_last_error(None).decode()
+    assert (got, message in text) == (status, True), (name, got, text)
+    assert not h
+
+
 def test_product_never_touches_the_oracle():
     """Only tests/, smoke() and bench.py's cpu_baseline leg may use oracle/."""
     pkg = os.path.join(REPO, "goblin_amd")
