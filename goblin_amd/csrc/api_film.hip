@@ -1,5 +1,5 @@
 // libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): what happens to a film after the render calls --
-// gbl_film_resolve, gbl_film_develop, gbl_film_variance, gbl_film_denoise, gbl_film_accumulate and the RCCL reduce of
+// gbl_film_resolve, gbl_film_develop, gbl_film_variance, gbl_film_denoise, gbl_film_accumulate, gbl_film_accumulate_motion and the RCCL reduce of
 // gbl_film_allreduce.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -104,10 +104,6 @@ static bool denoise_level_in_lds(int stride) {
     if (const char* e = getenv("GBL_DENOISE_LDS")) return e[0] != '0';
     return stride <= 2;
 }
-static bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
 static gbl_status gbl_film_denoise_impl(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* albedo_accum, const float* normal_accum,
                                         const float* depth_accum, const gbl_denoise_params* p, float* film_out) {
     if (!ctx) return GBL_ERR_INVALID;
@@ -163,40 +159,45 @@ gbl_status gbl_film_denoise(gbl_ctx* ctx, const float* film_accum, const float* 
 }
 
 // Reprojected temporal accumulation (kernels/temporal.h): prepare the current frame, then one kernel that gathers the history
-// and writes every output.
-static gbl_status gbl_film_accumulate_impl(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* normal_accum, const float* depth_accum,
+// and writes every output.  with_motion: gbl_film_accumulate_motion (`who` in the messages) -- the reprojection comes from the
+// planes of gbl_render_motion and params->prev_camera is not read.
+static gbl_status gbl_film_accumulate_impl(gbl_ctx* ctx, const char* name, bool with_motion, const float* motion, const float* film_accum,
+                                           const float* variance, const float* normal_accum, const float* depth_accum,
                                            const float* history_in, float* history_out, const gbl_temporal_params* p, float* film_out,
                                            float* variance_out) {
     if (!ctx) return GBL_ERR_INVALID;
-    if (!film_accum) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: film_accum is NULL");
-    if (!depth_accum) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: depth_accum is NULL");
-    if (!history_out) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: history_out is NULL");
-    if (!p) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: params is NULL");
-    if (!film_out) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: film_out is NULL");
+    const std::string who = std::string(name) + ": ";
+    if (!film_accum) return fail(ctx, GBL_ERR_INVALID, who + "film_accum is NULL");
+    if (!depth_accum) return fail(ctx, GBL_ERR_INVALID, who + "depth_accum is NULL");
+    if (!history_out) return fail(ctx, GBL_ERR_INVALID, who + "history_out is NULL");
+    if (!p) return fail(ctx, GBL_ERR_INVALID, who + "params is NULL");
+    if (!film_out) return fail(ctx, GBL_ERR_INVALID, who + "film_out is NULL");
     if (!std::isfinite(p->alpha_min) || !(p->alpha_min > 0.0f) || p->alpha_min > 1.0f)
-        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: alpha_min must be in (0, 1]");
-    if (!std::isfinite(p->max_history) || !(p->max_history >= 1.0f)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: max_history must be finite and >= 1");
-    if (!std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.0f)) return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: sigma_depth must be finite and > 0");
+        return fail(ctx, GBL_ERR_INVALID, who + "alpha_min must be in (0, 1]");
+    if (!std::isfinite(p->max_history) || !(p->max_history >= 1.0f)) return fail(ctx, GBL_ERR_INVALID, who + "max_history must be finite and >= 1");
+    if (!std::isfinite(p->sigma_depth) || !(p->sigma_depth > 0.0f)) return fail(ctx, GBL_ERR_INVALID, who + "sigma_depth must be finite and > 0");
     if (normal_accum && (!std::isfinite(p->cos_normal) || p->cos_normal < -1.0f || p->cos_normal > 1.0f))
-        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: cos_normal must be in [-1, 1]");
-    if (history_in && p->prev_camera.type > GBL_CAMERA_ORTHOGRAPHIC)
-        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: prev_camera.type: unknown camera type");
+        return fail(ctx, GBL_ERR_INVALID, who + "cos_normal must be in [-1, 1]");
+    if (with_motion && !motion) return fail(ctx, GBL_ERR_INVALID, who + "motion is NULL");
+    if (!with_motion && history_in && p->prev_camera.type > GBL_CAMERA_ORTHOGRAPHIC)
+        return fail(ctx, GBL_ERR_INVALID, who + "prev_camera.type: unknown camera type");
     const int width = ctx->info.xres, height = ctx->info.yres, n = width * height;
     const uint64_t film_bytes = static_cast<uint64_t>(n) * 4 * sizeof(float), plane_bytes = film_bytes / 4;
     const uint64_t history_bytes = static_cast<uint64_t>(n) * GBL_HISTORY_FLOATS_PER_PIXEL * sizeof(float);
     if (overlaps(history_out, history_bytes, history_in, history_bytes))
-        return fail(ctx, GBL_ERR_INVALID, "gbl_film_accumulate: history_out may not overlap history_in (the gather reads neighbours)");
+        return fail(ctx, GBL_ERR_INVALID, who + "history_out may not overlap history_in (the gather reads neighbours)");
     const struct { const void* p; uint64_t bytes; const char* name; } outs[3] = {{film_out, film_bytes, "film_out"}, {variance_out, plane_bytes, "variance_out"},
                                                                                   {history_out, history_bytes, "history_out"}},
-        ins[5] = {{film_accum, film_bytes, "film_accum"}, {variance, plane_bytes, "variance"}, {normal_accum, film_bytes, "normal_accum"},
-                  {depth_accum, film_bytes, "depth_accum"}, {history_in, history_bytes, "history_in"}};
+        ins[6] = {{film_accum, film_bytes, "film_accum"}, {variance, plane_bytes, "variance"}, {normal_accum, film_bytes, "normal_accum"},
+                  {depth_accum, film_bytes, "depth_accum"}, {history_in, history_bytes, "history_in"},
+                  {motion, static_cast<uint64_t>(n) * GBL_MOTION_FLOATS_PER_PIXEL * sizeof(float), "motion"}};
     for (int o = 0; o < 3; ++o) {
         for (const auto& in : ins)
             if (overlaps(outs[o].p, outs[o].bytes, in.p, in.bytes))
-                return fail(ctx, GBL_ERR_INVALID, std::string("gbl_film_accumulate: ") + outs[o].name + " may not overlap " + in.name);
+                return fail(ctx, GBL_ERR_INVALID, who + outs[o].name + " may not overlap " + in.name);
         for (int q = o + 1; q < 3; ++q)
             if (overlaps(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes))
-                return fail(ctx, GBL_ERR_INVALID, std::string("gbl_film_accumulate: ") + outs[o].name + " may not overlap " + outs[q].name);
+                return fail(ctx, GBL_ERR_INVALID, who + outs[o].name + " may not overlap " + outs[q].name);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = static_cast<hipStream_t>(p->stream);
@@ -212,21 +213,31 @@ static gbl_status gbl_film_accumulate_impl(gbl_ctx* ctx, const float* film_accum
     a.W = width;
     a.H = height;
     a.cur = ctx->scene.camera;
-    if (history_in) pack_camera(p->prev_camera, ctx->h_film, &a.prev);
+    if (history_in && !with_motion) pack_camera(p->prev_camera, ctx->h_film, &a.prev);
     a.alpha_min = p->alpha_min;
     a.max_history = p->max_history;
     a.sigma_depth = p->sigma_depth;
     a.cos_normal = p->cos_normal;
     a.has_normal = normal_accum ? 1u : 0u;
     a.has_history = history_in ? 1u : 0u;
-    gbl_launch_temporal_accumulate(!variance, cl, nz, fl, variance, history_in, history_out, film_out, variance_out, a, stream);
+    if (with_motion)
+        gbl_launch_temporal_accumulate_motion(!variance, cl, nz, fl, variance, history_in, history_out, film_out, variance_out, motion, a, stream);
+    else
+        gbl_launch_temporal_accumulate(!variance, cl, nz, fl, variance, history_in, history_out, film_out, variance_out, a, stream);
     HIP_TRY(ctx, hipGetLastError());
     return GBL_OK;
 }
 gbl_status gbl_film_accumulate(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* normal_accum, const float* depth_accum,
                                const float* history_in, float* history_out, const gbl_temporal_params* params, float* film_out, float* variance_out) {
-    return gbl_guard([&] { return gbl_film_accumulate_impl(ctx, film_accum, variance, normal_accum, depth_accum, history_in, history_out, params, film_out,
-                                                           variance_out); },
+    return gbl_guard([&] { return gbl_film_accumulate_impl(ctx, "gbl_film_accumulate", false, nullptr, film_accum, variance, normal_accum, depth_accum,
+                                                           history_in, history_out, params, film_out, variance_out); },
+                     [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+gbl_status gbl_film_accumulate_motion(gbl_ctx* ctx, const float* film_accum, const float* variance, const float* normal_accum, const float* depth_accum,
+                                      const float* history_in, float* history_out, const float* motion, const gbl_temporal_params* params, float* film_out,
+                                      float* variance_out) {
+    return gbl_guard([&] { return gbl_film_accumulate_impl(ctx, "gbl_film_accumulate_motion", true, motion, film_accum, variance, normal_accum, depth_accum,
+                                                           history_in, history_out, params, film_out, variance_out); },
                      [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 

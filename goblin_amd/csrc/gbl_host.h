@@ -1,5 +1,5 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
-// api_film.hip) share.  No kernel header is needed to read it.
+// api_film.hip, api_motion.hip) share.  No kernel header is needed to read it.
 #pragma once
 #include <string>
 
@@ -22,6 +22,12 @@ gbl_status allow_lds(gbl_ctx* ctx, K kernel, size_t bytes) {
     if (bytes > 64 * 1024)
         HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
     return GBL_OK;
+}
+
+// Two byte ranges share a byte; false when either pointer is NULL
+inline bool overlaps(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 // LDS of a workgroup's traversal stacks

@@ -16,6 +16,7 @@
 #include "kernels/aov_args.h"
 #include "kernels/denoise_args.h"
 #include "kernels/temporal_args.h"
+#include "kernels/motion_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -62,6 +63,8 @@ struct gbl_ctx {
     gbl_buf denoise;          // gbl_film_denoise's four float4 planes (kernels/denoise.h): cv ping, cv pong, nz, af
     bool denoise_lds_allowed = false;   // ... its staging level kernel may be launched with more than 64 KB of LDS on this device
     gbl_buf temporal;         // gbl_film_accumulate's prepared frame (kernels/temporal.h): cl, nz (float4 each) and the flags
+    gbl_buf motion;           // gbl_render_motion's previous-transform table and moved flags (kernels/motion_args.h) ...
+    std::vector<unsigned char> h_motion;   // ... and the host copy they are uploaded from
     std::map<int, float> auto_rays_per_path;   // GBL_SCHEDULE_AUTO's pilot: rays per camera path by 2 * max_ray_depth + russian_roulette (gbl_render)
     double build_ms = 0.0;    // pack_scene + BVH construction + node / triangle upload
     // what gbl_update_camera and gbl_film_accumulate need to pack a camera (scene_prep.h pack_camera)
@@ -102,6 +105,7 @@ typedef void (*gbl_render_kernel)(DevScene, RenderArgs);
 typedef void (*gbl_wf_kernel)(DevScene, RenderArgs, WfArgs);
 typedef void (*gbl_li_kernel)(DevScene, RenderArgs, float4*);
 typedef void (*gbl_aov_kernel)(DevScene, RenderArgs, AovArgs);
+typedef void (*gbl_motion_kernel)(DevScene, MotionArgs);
 
 // kernels_path.hip: the persistent megakernel and the AO kernel (kernels/render_kernels.h), native / replay samplers
 gbl_render_kernel gbl_kernel_path(bool replay, bool stats, bool ext, bool exact_ties = false);
@@ -154,6 +158,12 @@ void gbl_launch_temporal_prepare(const float* film, const float* variance, const
                                  int n, hipStream_t stream);
 void gbl_launch_temporal_accumulate(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance, const float* history_in,
                                     float* history_out, float* film_out, float* variance_out, const TemporalArgs& a, hipStream_t stream);
+// kernels_motion.hip: gbl_render_motion's kernels (kernels/motion.h) -- the packet kernel, or one ray per lane, lean or EXT -- and
+// gbl_film_accumulate_motion's accumulate pass (kernels/temporal.h with the reprojection read from the motion planes)
+gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext);
+void gbl_launch_temporal_accumulate_motion(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance,
+                                           const float* history_in, float* history_out, float* film_out, float* variance_out, const float* motion,
+                                           const TemporalArgs& a, hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

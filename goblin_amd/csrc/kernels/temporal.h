@@ -53,6 +53,32 @@ __device__ __forceinline__ void tp_camera_ray(const DevCamera& c, float image_x,
     *d = tp_quat_rotate(c.q[0], c.q[1], c.q[2], c.q[3], normalize(f3(xv, yv, 1.0f)));
 }
 
+// The projection of a world point through a packed camera, as the reprojection of temporal_accumulate_kernel states it below
+// (w, v, the `front` rule per camera type, xndc, yndc, z_exp, image_x, image_y).  Returns `front`; kernels/motion.h writes what
+// this returns into its planes, so the two accumulate calls see the same numbers.
+__device__ __forceinline__ bool tp_project(const DevCamera& prev, F3 P, int W, int H, float* image_x, float* image_y, float* z_exp_out) {
+    const F3 w = P - f3(prev.pos[0], prev.pos[1], prev.pos[2]);
+    const F3 v = tp_quat_rotate(prev.q[0], -prev.q[1], -prev.q[2], -prev.q[3], w);
+    float xndc, yndc, z_exp;
+    bool front;
+    if (prev.type == 1u) {
+        front = v.z >= 0.0f;
+        xndc = v.x / (0.5f * prev.film_w);
+        yndc = v.y / (0.5f * prev.film_h);
+        z_exp = v.z;
+    } else {
+        front = v.z > 0.0f;
+        xndc = (v.x / v.z) * prev.proj00;
+        yndc = (v.y / v.z) * prev.proj11;
+        z_exp = sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z);
+    }
+    *image_x = ((xndc + 1.0f) * 0.5f) * static_cast<float>(W);
+    *image_y = ((1.0f - yndc) * 0.5f) * static_cast<float>(H);
+    *z_exp_out = z_exp;
+    return front;
+}
+
+#ifndef GBL_TEMPORAL_NO_PREPARE   // (kernels_motion.hip includes this header for everything but the one kernel that is no template)
 __global__ void temporal_prepare_kernel(const float4* __restrict__ film, const float* __restrict__ variance, const float4* __restrict__ normal,
                                         const float4* __restrict__ depth, float4* __restrict__ cl, float4* __restrict__ nz, uint32_t* __restrict__ fl,
                                         int n) {
@@ -90,6 +116,7 @@ __global__ void temporal_prepare_kernel(const float4* __restrict__ film, const f
     nz[i] = make_float4(nx, ny, nzz, z);
     fl[i] = (valid ? GBL_TP_VALID : 0u) | (surf ? GBL_TP_SURF : 0u);
 }
+#endif
 
 // Per valid pixel p = (x, y) with colour c, luminance l, normal n, depth z:
 //   reproject  (covered p, history given)  (o, d) = the context camera's ray through (x + 0.5f, y + 0.5f); P = o + d * z;
@@ -108,10 +135,14 @@ __global__ void temporal_prepare_kernel(const float4* __restrict__ film, const f
 //              of valid q with p's SURF and, on a covered p, |z_q - z_p| <= sigma_depth * z_p:  mean = (sum l) / m,
 //              s2 = (sum (l - mean)^2) / (m - 1), 0 for m < 2
 // An invalid pixel writes zeros to every output.
-template <bool SPATIAL>
-__global__ __launch_bounds__(GBL_TP_TILE_W * GBL_TP_TILE_H) void temporal_accumulate_kernel(
-    const float4* __restrict__ cl, const float4* __restrict__ nz, const uint32_t* __restrict__ fl, const float* __restrict__ variance,
-    const float4* __restrict__ hist_in, float4* __restrict__ hist_out, float4* __restrict__ film_out, float* __restrict__ variance_out, TemporalArgs a) {
+// MOTION (gbl_film_accumulate_motion): the reprojection is read from the planes of gbl_render_motion instead --
+// (image_x, image_y, z_exp) = M0.xyz, no history where M0.w == 0 -- and, with a normal film, the taps are tested against M1.xyz, the
+// current normal carried into the previous frame; H2 still stores n.  `motion` is not read otherwise.
+template <bool SPATIAL, bool MOTION>
+__device__ __forceinline__ void tp_accumulate(const float4* __restrict__ cl, const float4* __restrict__ nz, const uint32_t* __restrict__ fl,
+                                              const float* __restrict__ variance, const float4* __restrict__ hist_in, float4* __restrict__ hist_out,
+                                              float4* __restrict__ film_out, float* __restrict__ variance_out, const float4* __restrict__ motion,
+                                              const TemporalArgs& a) {
     constexpr int SW = GBL_TP_TILE_W + 2 * GBL_TP_HALO, SH = GBL_TP_TILE_H + 2 * GBL_TP_HALO;
     __shared__ float s_l[SPATIAL ? SW * SH : 1];
     __shared__ float s_z[SPATIAL ? SW * SH : 1];
@@ -152,26 +183,24 @@ __global__ __launch_bounds__(GBL_TP_TILE_W * GBL_TP_TILE_H) void temporal_accumu
     // ---- reproject and gather
     float ws = 0.0f, pr = 0.0f, pg = 0.0f, pb = 0.0f, pN = 0.0f, pm1 = 0.0f, pm2 = 0.0f, pv = 0.0f;
     if (a.has_history && surf) {
-        F3 o, d;
-        tp_camera_ray(a.cur, static_cast<float>(x) + 0.5f, static_cast<float>(y) + 0.5f, &o, &d);
-        const F3 P = o + d * z;
-        const F3 w = P - f3(a.prev.pos[0], a.prev.pos[1], a.prev.pos[2]);
-        const F3 v = tp_quat_rotate(a.prev.q[0], -a.prev.q[1], -a.prev.q[2], -a.prev.q[3], w);
-        float xndc, yndc, z_exp;
+        float image_x, image_y, z_exp;
         bool front;
-        if (a.prev.type == 1u) {
-            front = v.z >= 0.0f;
-            xndc = v.x / (0.5f * a.prev.film_w);
-            yndc = v.y / (0.5f * a.prev.film_h);
-            z_exp = v.z;
+        F3 nt = f3(np.x, np.y, np.z);   // the normal the taps are tested against
+        if constexpr (MOTION) {
+            const float4 m0 = motion[pi];
+            image_x = m0.x;
+            image_y = m0.y;
+            z_exp = m0.z;
+            front = m0.w != 0.0f;
+            if (a.has_normal) {
+                const float4 m1 = motion[n + pi];
+                nt = f3(m1.x, m1.y, m1.z);
+            }
         } else {
-            front = v.z > 0.0f;
-            xndc = (v.x / v.z) * a.prev.proj00;
-            yndc = (v.y / v.z) * a.prev.proj11;
-            z_exp = sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z);
+            F3 o, d;
+            tp_camera_ray(a.cur, static_cast<float>(x) + 0.5f, static_cast<float>(y) + 0.5f, &o, &d);
+            front = tp_project(a.prev, o + d * z, W, H, &image_x, &image_y, &z_exp);
         }
-        const float image_x = ((xndc + 1.0f) * 0.5f) * static_cast<float>(W);
-        const float image_y = ((1.0f - yndc) * 0.5f) * static_cast<float>(H);
         const float fx = image_x - 0.5f, fy = image_y - 0.5f;
         const float x0f = floorf(fx), y0f = floorf(fy);
         // the float compares keep the conversion to int defined; taps of a footprint beyond them lie outside the image anyway
@@ -191,7 +220,7 @@ __global__ __launch_bounds__(GBL_TP_TILE_W * GBL_TP_TILE_H) void temporal_accumu
                     if (!(h2.w != 0.0f)) continue;
                     const float4 h1 = hist_in[n + qi];
                     if (!(fabsf(h1.w - z_exp) <= ztol)) continue;
-                    if (a.has_normal && !((np.x * h2.x + np.y * h2.y) + np.z * h2.z >= a.cos_normal)) continue;
+                    if (a.has_normal && !((nt.x * h2.x + nt.y * h2.y) + nt.z * h2.z >= a.cos_normal)) continue;
                     const float b = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);
                     ws += b;
                     pr += b * h0.x;
@@ -274,4 +303,19 @@ __global__ __launch_bounds__(GBL_TP_TILE_W * GBL_TP_TILE_H) void temporal_accumu
     hist_out[pi] = make_float4(cr, cg, cb, N);
     hist_out[n + pi] = make_float4(m1, m2, v_out, z);
     hist_out[2 * n + pi] = make_float4(np.x, np.y, np.z, surf ? 1.0f : 0.0f);
+}
+
+template <bool SPATIAL>
+__global__ __launch_bounds__(GBL_TP_TILE_W * GBL_TP_TILE_H) void temporal_accumulate_kernel(
+    const float4* __restrict__ cl, const float4* __restrict__ nz, const uint32_t* __restrict__ fl, const float* __restrict__ variance,
+    const float4* __restrict__ hist_in, float4* __restrict__ hist_out, float4* __restrict__ film_out, float* __restrict__ variance_out, TemporalArgs a) {
+    tp_accumulate<SPATIAL, false>(cl, nz, fl, variance, hist_in, hist_out, film_out, variance_out, nullptr, a);
+}
+// ... and with the reprojection read from gbl_render_motion's planes (instantiated in kernels_motion.hip)
+template <bool SPATIAL>
+__global__ __launch_bounds__(GBL_TP_TILE_W * GBL_TP_TILE_H) void temporal_accumulate_motion_kernel(
+    const float4* __restrict__ cl, const float4* __restrict__ nz, const uint32_t* __restrict__ fl, const float* __restrict__ variance,
+    const float4* __restrict__ hist_in, float4* __restrict__ hist_out, float4* __restrict__ film_out, float* __restrict__ variance_out,
+    const float4* __restrict__ motion, TemporalArgs a) {
+    tp_accumulate<SPATIAL, true>(cl, nz, fl, variance, hist_in, hist_out, film_out, variance_out, motion, a);
 }

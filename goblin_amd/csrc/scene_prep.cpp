@@ -764,6 +764,17 @@ gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err) {
     return GBL_OK;
 }
 
+bool pack_transform(const gbl_trs& to_world, uint32_t i, float m[12], float inv[12], std::string* err) {
+    gbl_instance gi;
+    memset(&gi, 0, sizeof(gi));
+    gi.to_world = to_world;
+    Trs t;
+    if (!instance_transform(gi, i, &t, err)) return false;
+    store3x4(t.m, m);
+    store3x4(t.inv, inv);
+    return true;
+}
+
 bool camera_extended(const gbl_camera& c) { return c.lens_radius != 0.0f || c.type != GBL_CAMERA_PERSPECTIVE; }
 
 void pack_camera(const gbl_camera& c, const gbl_film& film, DevCamera* out) {

@@ -79,6 +79,10 @@ struct TlasResult {
 // Refuses (GBL_ERR_INVALID, *err set, *out unspecified) an instance whose transform the reference cannot invert.
 gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err);
 
+// The 3x4 rows of a transform and of its inverse as build_tlas composes them for DevInstance::m / inv (gbl_render_motion's
+// previous transforms).  false, *err set to build_tlas's refusal for instance i, when the reference cannot invert it.
+bool pack_transform(const gbl_trs& to_world, uint32_t i, float m[12], float inv[12], std::string* err);
+
 // Traversal stack entries a scene needs (kernels/trace.h): exit marker + the worst root-to-leaf sum over the TLAS nodes
 // (tlas[0..] are the nodes at absolute indices tlas_base + i) of (children - 1), + per instance its sentinel and what its
 // mesh's BLAS needs, + one spare.

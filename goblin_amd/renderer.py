@@ -81,6 +81,16 @@ class HipPathTracer:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         self.lib.gbl_get_info(self.handle, C.byref(self.info))
 
+    def instances(self):
+        """The transforms the context holds now (gbl_get_instances): a list of (position, orientation wxyz, scale) tuples, one per
+        instance -- the scene's at first, the edited ones after ``update_instances``.  What ``motion`` takes as ``prev_instances``."""
+        n = int(self.info.instances)
+        arr = (_abi.gbl_trs * max(n, 1))()
+        st = self.lib.gbl_get_instances(self.handle, 0, n, arr)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, "gbl_get_instances")
+        return [(tuple(arr[i].position), tuple(arr[i].orientation), tuple(arr[i].scale)) for i in range(n)]
+
     def camera(self):
         """The camera description last set (gbl_get_camera): a gbl_camera, the scene's at first."""
         cam = _abi.gbl_camera()
@@ -339,14 +349,47 @@ class HipPathTracer:
         torch = _torch()
         return torch.zeros((3, self.info.yres, self.info.xres, 4), dtype=torch.float32, device=self.device)
 
+    def motion(self, prev_camera, prev_instances=None, normal=None):
+        """Motion planes of the current frame (gbl_render_motion) on the current stream: a (2, yres, xres, 4) float32 tensor --
+        [0] = {image_x, image_y, z_exp, ok}, where the surface under each pixel's centre lay under ``prev_camera`` (a gbl_camera)
+        and, for an instance that moved since, under its transform in ``prev_instances`` (``instances()`` as it was when the
+        previous frame was rendered; None: no instance moved); [1] = {the current normal carried into the previous frame, instance
+        + 1 or 0}, the normal taken from ``normal`` (render_aov's film; zeros without one).  ``accumulate(motion=...)`` reads it."""
+        torch = _torch()
+        h, w = self.info.yres, self.info.xres
+        p = _abi.gbl_motion_params()
+        p.prev_camera = prev_camera
+        arr = None
+        if prev_instances is not None:
+            if len(prev_instances) != int(self.info.instances):
+                raise ValueError("prev_instances must hold one transform per instance (%d)" % int(self.info.instances))
+            arr = (_abi.gbl_trs * max(len(prev_instances), 1))()
+            for i, (pos, quat, scale) in enumerate(prev_instances):
+                arr[i].position[:] = pos
+                arr[i].orientation[:] = quat
+                arr[i].scale[:] = scale
+            p.prev_to_world = arr
+        if normal is not None:
+            normal = normal.accum if isinstance(normal, Film) else normal
+            if tuple(normal.shape) != (h, w, 4) or normal.dtype != torch.float32 or normal.device != self.device or not normal.is_contiguous():
+                raise ValueError("normal must be a contiguous (%d, %d, 4) float32 tensor on %s" % (h, w, self.device))
+            p.normal_accum = normal.data_ptr()
+        p.stream = torch.cuda.current_stream(self.device).cuda_stream
+        out = torch.empty((2, h, w, 4), dtype=torch.float32, device=self.device)
+        st = self.lib.gbl_render_motion(self.handle, C.byref(p), out.data_ptr())
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return out
+
     def accumulate(self, film, depth, variance=None, normal=None, history=None, prev_camera=None, alpha_min=0.1, max_history=64.0,
-                   sigma_depth=0.05, cos_normal=0.9):
+                   sigma_depth=0.05, cos_normal=0.9, motion=None):
         """Reprojected temporal accumulation (gbl_film_accumulate) on the current stream: blends the frame ``film`` (rendered
         under the tracer's current camera) into ``history``, the "history" a previous call returned, fetched from where each
         pixel's surface lay under ``prev_camera`` (a gbl_camera: ``camera()`` as it was when that frame was rendered).
         ``depth`` and ``normal`` are render_aov's films, ``variance`` the plane of ``variance()``; without it the variance is
         estimated from the accumulated luminance moments and the current frame's neighbourhood.  history=None starts a
-        sequence.  Returns {"film": Film {rgb, 1} (``denoise``, ``normalized`` and ``develop`` take it as a rendered one),
+        sequence.  ``motion``: the planes ``motion()`` returned for this frame -- the history is then fetched from where they say
+        (gbl_film_accumulate_motion), which carries moved instances along, and ``prev_camera`` is not needed.  Returns {"film": Film {rgb, 1} (``denoise``, ``normalized`` and ``develop`` take it as a rendered one),
         "variance": (yres, xres) variance of the accumulated pixel, "history": the new history (the input one is not touched)}."""
         torch = _torch()
         h, w = self.info.yres, self.info.xres
@@ -363,7 +406,8 @@ class HipPathTracer:
             raise ValueError("accumulate needs a film and a depth film")
         var, nrm = plane(variance, (h, w), "variance"), plane(normal, (h, w, 4), "normal")
         hist = plane(history, (3, h, w, 4), "history")
-        if hist is not None and prev_camera is None:
+        mo = plane(motion, (2, h, w, 4), "motion")
+        if hist is not None and prev_camera is None and mo is None:
             raise ValueError("a history needs the camera it was accumulated under (prev_camera)")
         p = _abi.gbl_temporal_params()
         if prev_camera is not None:
@@ -377,8 +421,12 @@ class HipPathTracer:
 
         def ptr(t):
             return t.data_ptr() if t is not None else None
-        st = self.lib.gbl_film_accumulate(self.handle, accum.data_ptr(), ptr(var), ptr(nrm), dep.data_ptr(), ptr(hist), hist_out.data_ptr(),
-                                          C.byref(p), out.accum.data_ptr(), var_out.data_ptr())
+        if mo is not None:
+            st = self.lib.gbl_film_accumulate_motion(self.handle, accum.data_ptr(), ptr(var), ptr(nrm), dep.data_ptr(), ptr(hist), hist_out.data_ptr(),
+                                                     mo.data_ptr(), C.byref(p), out.accum.data_ptr(), var_out.data_ptr())
+        else:
+            st = self.lib.gbl_film_accumulate(self.handle, accum.data_ptr(), ptr(var), ptr(nrm), dep.data_ptr(), ptr(hist), hist_out.data_ptr(),
+                                              C.byref(p), out.accum.data_ptr(), var_out.data_ptr())
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return {"film": out, "variance": var_out, "history": hist_out}

@@ -595,8 +595,8 @@ gbl_status gbl_film_denoise(gbl_ctx* ctx, const float* film_accum, const float* 
  * from `variance` where that plane is given, otherwise estimated from the accumulated luminance moments (N >= 4) or from the
  * 5 x 5 neighbourhood of the current frame -- a variance for films that arrive without per-sample radiance.  Limits: a thin
  * lens is reprojected as its pinhole; pixels without coverage (the background) do not accumulate; moving instances are not
- * reprojected, a moved instance ghosts until the depth or normal test rejects it.  No output may overlap an input or another
- * output.  Asynchronous on params->stream; the scratch lives in the context: calls that share a context are ordered by the
+ * reprojected here, a moved instance ghosts until the depth or normal test rejects it: gbl_render_motion and
+ * gbl_film_accumulate_motion below carry them.  No output may overlap an input or another output.  Asynchronous on params->stream; the scratch lives in the context: calls that share a context are ordered by the
  * caller. */
 #define GBL_HISTORY_FLOATS_PER_PIXEL 12   /* three float4 planes of xres*yres, caller-owned, device memory */
 typedef struct gbl_temporal_params {
@@ -613,6 +613,48 @@ gbl_status gbl_film_accumulate(gbl_ctx* ctx, const float* film_accum, const floa
                                const float* history_in /* or NULL: first frame */, float* history_out,
                                const gbl_temporal_params* params, float* film_out /* float4, {rgb, 1} */,
                                float* variance_out /* xres*yres, or NULL */);
+
+/* Motion planes: per image pixel, where the surface point under the pixel's centre lay in the previous frame --
+ * under params->prev_camera and, for an instance whose transform changed since, under its previous transform.  The ray is the
+ * context camera's through (x + 0.5, y + 0.5), pinhole or orthographic (a thin lens counts as its pinhole), traced as
+ * gbl_render_aov traces a camera ray without exact_ties.  On a hit of instance i at P: P_prev = M_prev[i] (Minv_cur[i] P) if the
+ * instance moved, else P itself, projected through prev_camera exactly as gbl_film_accumulate projects its point.
+ * motion_out is two planes of xres*yres float4 in device memory, one after the other:
+ *   M0 = {image_x, image_y, z_exp, ok}   ok = 1 iff the ray hit, P_prev lies in front of prev_camera and all three are finite;
+ *                                        otherwise the texel is all zeros
+ *   M1 = {n_b.xyz, instance + 1}         0 in .w on a miss.  n_b: the current frame's normal (normal_accum resolved as
+ *                                        gbl_film_accumulate resolves it; zeros without one) carried into the previous frame by
+ *                                        the inverse transpose of the same pair of transforms, unit length or 0; n itself for an
+ *                                        unmoved instance and on a miss
+ * prev_to_world: one gbl_trs per instance of the context (what gbl_get_instances returned when the previous frame was
+ * rendered), or NULL: no instance moved.  An instance moved iff its ten floats differ bitwise from the current ones, so a static
+ * scene is reprojected without a round trip through two matrices.  GBL_ERR_INVALID: a NULL params or motion_out, motion_out
+ * overlapping normal_accum, an unknown prev_camera.type, a non-finite previous transform and one the reference cannot invert
+ * (|det| < 1e-5, as gbl_create refuses it); GBL_ERR_UNSUPPORTED: 2^24 - 1 or more instances (the id must be exact in a float).
+ * Always the whole image: no window, no shard -- the planes are not accumulators, so with several GPUs every rank computes
+ * them.  Asynchronous on params->stream (the table of previous transforms is uploaded from pageable memory when an instance
+ * moved); that table lives in the context: calls that share a context are ordered by the caller. */
+#define GBL_MOTION_FLOATS_PER_PIXEL 8   /* two float4 planes of xres*yres, caller-owned, device memory */
+typedef struct gbl_motion_params {
+    gbl_camera prev_camera;        /* the camera of the previous frame */
+    const gbl_trs* prev_to_world;  /* host, one per instance, or NULL: no instance moved */
+    const float* normal_accum;     /* device, the current frame's normal film, or NULL */
+    void* stream;                  /* hipStream_t, NULL = default stream */
+} gbl_motion_params;
+gbl_status gbl_render_motion(gbl_ctx* ctx, const gbl_motion_params* params, float* motion_out);
+
+/* gbl_film_accumulate with the reprojection read from `motion` (gbl_render_motion's planes for this frame) instead of
+ * computed from the depth film and params->prev_camera, which is not read: (image_x, image_y, z_exp) = M0.xyz, a pixel with
+ * M0.w == 0 has no history, and with a normal film the taps are tested against M1.xyz in place of n (H2 still stores n).
+ * Everything else is gbl_film_accumulate's, word for word: prepare, the four taps and their order, blend, both variance
+ * paths, outputs and refusals, to which a NULL `motion` and one overlapping an output are added.  The history planes keep their
+ * layout, so a history may pass between the two calls.  Limits: taps are not rejected by instance id (M1.w is for the caller);
+ * the depth a tap is tested against is the centre ray's, not the filtered film's. */
+gbl_status gbl_film_accumulate_motion(gbl_ctx* ctx, const float* film_accum, const float* variance /* or NULL */,
+                                      const float* normal_accum /* or NULL */, const float* depth_accum,
+                                      const float* history_in /* or NULL: first frame */, float* history_out,
+                                      const float* motion /* gbl_render_motion's planes */, const gbl_temporal_params* params,
+                                      float* film_out /* float4, {rgb, 1} */, float* variance_out /* xres*yres, or NULL */);
 
 /* Device time of recent gbl_render calls, from HIP events recorded on the render stream
  * around the dominant kernel and around the whole call (no host synchronisation happens
@@ -646,6 +688,10 @@ gbl_status gbl_get_info(const gbl_ctx* ctx, gbl_info* out);
  * the device.  Instances that carry an area light, and scenes with a directional or image based light (whose power and
  * sampling sphere depend on the scene bound), are GBL_ERR_UNSUPPORTED: re-create the context for those. */
 gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world);
+/* The transforms the context holds now for instances [first, first + count): gbl_create's at first, the edited ones after
+ * gbl_update_instances.  Host only.  What a caller keeps, next to the camera, as "the previous frame" for gbl_render_motion: the
+ * context holds no frame state.  GBL_ERR_INVALID for a NULL argument or a range out of bounds. */
+gbl_status gbl_get_instances(const gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_trs* out);
 
 /* Camera edit: every later call on the context sees `camera`; film and resolution stay the context's.  Host work only (the
  * scene is neither rebuilt nor uploaded) and no device synchronisation: every kernel receives the camera by value, so work
