@@ -594,6 +594,7 @@ template <int SAMPLER, bool STATS, bool EXT, bool QUAD = false, bool EXACT = fal
 __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void path_trace_kernel(DevScene sc, RenderArgs ra) {
     constexpr bool REPLAY = SAMPLER != GBL_SRC_NATIVE, STREAM = SAMPLER == GBL_SRC_STREAM, TIES = REPLAY || STATS || EXACT || EXT;
     constexpr bool WAVE = QUAD && SAMPLER == GBL_SRC_NATIVE && GBL_WAVE_UNITS;   // wave-owned work units (below); else the workgroup's item loop
+    constexpr bool LAST_SKIP = SAMPLER == GBL_SRC_NATIVE && !STATS && !EXT;      // the capped vertex traces no ray under a delta light (below)
     extern __shared__ __align__(16) unsigned char smem[];
     const int tp = GBL_TILE + 2 * sc.film.halo;
     float* tile = reinterpret_cast<float*>(smem);
@@ -1046,6 +1047,21 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                 if (STREAM && !occluded) {   // evalAttenuation(scene, shadowRay, BSDFSample(rng)), :101-103
                     stream_draws += 3;
                     path_draws += 3;
+                }
+            }
+            // ---- the last vertex under a delta light: no next ray
+            // The vertex at bounce max_depth - 2 is the last one the loop shades: its extension ray's hit is only ever looked at by the
+            // close step's MIS test, instances[hit].area_light == ps.light, which no hit passes when the picked light is a spot, point
+            // or directional light (an instance's area_light names an area light: validate_desc).  What the close step would add one
+            // iteration later -- with or without a hit, and whatever the roulette below decides -- is the dead-end term, so the lane
+            // adds it here, in the same order, and ends: no mat_sample, no light_pdf, no ray.  Per lane: beside an area light the
+            // lanes that picked it still trace.  The lean native kernels only; the instrumented, replay, stream and EXT builds
+            // go on tracing the reference's ray (its counters, its draws, the IBL term) and are what the lean ones are tested against.
+            if constexpr (LAST_SKIP) {
+                if (vis && !finished && ps.bounce + 1 >= ra.max_depth - 1 && light_is_delta<EXT>(sc.lights[ps.light])) {
+                    F3 add = div(ps.throughput * ps.Ld, ps.pick_pdf);
+                    ps.Li = f3(ps.Li.x + add.x, ps.Li.y + add.y, ps.Li.z + add.z);
+                    finished = true;
                 }
             }
             // ---- BSDF sample: the next ray

@@ -651,6 +651,11 @@ gbl_status validate_lights(const gbl_scene_desc& d, std::string* err) {
             return refuse(GBL_ERR_INVALID, "image based light " + std::to_string(i) + ": bad image index", err);
         if (gl.type > GBL_LIGHT_IBL) return refuse(GBL_ERR_INVALID, "unknown light type", err);
     }
+    // an emissive instance emits through an AREA light: the path kernels' MIS test instances[hit].area_light == picked light
+    // can then only hold for an area light (render_kernels.h skips the capped vertex's ray on that ground)
+    for (uint32_t i = 0; i < d.num_instances; ++i)
+        if (d.instances[i].area_light >= 0 && d.lights[d.instances[i].area_light].type != GBL_LIGHT_AREA)
+            return refuse(GBL_ERR_INVALID, "instance " + std::to_string(i) + ": area_light names a light that is not an area light", err);
     return GBL_OK;
 }
 
