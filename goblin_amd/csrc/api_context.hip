@@ -46,6 +46,41 @@ gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what) {
     return GBL_OK;
 }
 
+gbl_status rebuild_tlas(gbl_ctx* ctx, std::vector<gbl_instance>& edited, const char* who) {
+    const TlasInput in = {edited.data(),       static_cast<uint32_t>(edited.size()), ctx->h_meshes.data(),  ctx->h_materials.data(),
+                          ctx->mesh_lo.data(), ctx->mesh_hi.data(),                  ctx->mesh_root.data(), ctx->tlas_base};
+    TlasResult built;
+    std::string err;
+    gbl_status st = build_tlas(in, &built, &err);
+    if (st != GBL_OK) {
+        ctx->error = err;
+        return st;
+    }
+    const std::vector<DevInstance>& inst = built.instances;
+    const std::vector<DevNode>& tlas = built.nodes;
+    const std::vector<DevInstanceBound>& bounds = built.instance_bounds;
+    if (tlas.size() > ctx->tlas_capacity) {
+        ctx->error = std::string(who) + ": rebuilt TLAS does not fit its reserved nodes";
+        return GBL_ERR_DEVICE;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the old TLAS
+    DevScene& sc = ctx->scene;
+    if (!inst.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstance*>(sc.instances), inst.data(), inst.size() * sizeof(DevInstance), hipMemcpyHostToDevice));
+    if (!bounds.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstanceBound*>(sc.instance_bounds), bounds.data(), bounds.size() * sizeof(DevInstanceBound), hipMemcpyHostToDevice));
+    if (!tlas.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevNode*>(sc.nodes) + ctx->tlas_base, tlas.data(), tlas.size() * sizeof(DevNode), hipMemcpyHostToDevice));
+    sc.tlas_root = built.root;
+    sc.stack_entries = scene_stack_entries(tlas, ctx->tlas_base, built.root, inst, ctx->mesh_stack_need);   // (the wavefront stack backing is re-checked at render time)
+    ctx->info.tlas_depth = built.depth;
+    ctx->info.tlas_nodes = tlas.size();
+    ctx->h_instances.swap(edited);
+    ctx->auto_rays_per_path.clear();   // the edited scene's paths may be longer or shorter: AUTO measures again
+    return GBL_OK;
+}
+
 namespace {
 thread_local std::string g_create_error;
 
@@ -122,6 +157,7 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
     if (!device_bvh) {
         if ((st = upload(ctx, packed.nodes, &sc.nodes)) != GBL_OK) return bail(st);
         if ((st = upload(ctx, packed.tris, &sc.tris)) != GBL_OK) return bail(st);
+        ctx->num_nodes = packed.nodes.size();
     } else {
         // nodes = [TLAS (from the host) | mesh 0 | mesh 1 | ...], tris = every mesh's triangles in Morton order
         size_t node_cap = packed.nodes.size(), tri_cap = 0;
@@ -132,6 +168,7 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
             }
         // device buffers are allocated at their final size; only the TLAS nodes and the raw geometry cross PCIe
         if ((st = upload_raw(ctx, packed.nodes.data(), packed.nodes.size(), node_cap, &sc.nodes)) != GBL_OK) return bail(st);
+        ctx->num_nodes = node_cap;
         if ((st = upload_raw(ctx, static_cast<const DevTri*>(nullptr), 0, tri_cap, &sc.tris)) != GBL_OK) return bail(st);
         const float* d_pos = nullptr;
         const uint32_t* d_idx = nullptr;
@@ -241,6 +278,21 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
     ctx->tlas_capacity = packed.tlas_capacity;
     ctx->blas_depth = packed.blas_max_depth;
     ctx->mesh_stack_need = packed.mesh_stack_need;
+    // what gbl_update_vertices needs (api_geometry.hip)
+    ctx->h_positions.assign(desc->positions, desc->positions + 3 * static_cast<size_t>(desc->num_vertices));
+    ctx->h_indices.assign(desc->indices, desc->indices + 3 * static_cast<size_t>(desc->num_triangles));
+    ctx->mesh_tri_first.assign(desc->num_meshes, 0u);
+    ctx->mesh_emits.assign(desc->num_meshes, 0);
+    for (uint32_t m = 0, tri_first = 0; m < desc->num_meshes; ++m)
+        if (desc->meshes[m].shape == GBL_SHAPE_MESH) {
+            ctx->mesh_tri_first[m] = tri_first;
+            tri_first += desc->meshes[m].tri_count;
+        }
+    for (uint32_t i = 0; i < desc->num_instances; ++i)
+        if (desc->instances[i].area_light >= 0) ctx->mesh_emits[desc->instances[i].mesh] = 1;
+    for (uint32_t i = 0; i < desc->num_lights; ++i)
+        if (desc->lights[i].type == GBL_LIGHT_AREA && desc->lights[i].mesh < desc->num_meshes) ctx->mesh_emits[desc->lights[i].mesh] = 1;
+    ctx->refit.assign(desc->num_meshes, gbl_ctx::MeshRefit());
     if (getenv("GBL_PROBE"))
         fprintf(stderr, "probe: traversal stack entries %d (per-level bound %d: TLAS depth %d, BLAS depth %d)\n", packed.stack_entries,
                 3 * (packed.tlas_depth + packed.blas_max_depth) + 2, packed.tlas_depth, packed.blas_max_depth);
@@ -277,38 +329,7 @@ static gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32
         }
     std::vector<gbl_instance> edited = ctx->h_instances;
     for (uint32_t i = 0; i < count; ++i) edited[first + i].to_world = to_world[i];
-    const TlasInput in = {edited.data(),       static_cast<uint32_t>(edited.size()), ctx->h_meshes.data(),  ctx->h_materials.data(),
-                          ctx->mesh_lo.data(), ctx->mesh_hi.data(),                  ctx->mesh_root.data(), ctx->tlas_base};
-    TlasResult built;
-    std::string err;
-    gbl_status st = build_tlas(in, &built, &err);
-    if (st != GBL_OK) {
-        ctx->error = err;
-        return st;
-    }
-    const std::vector<DevInstance>& inst = built.instances;
-    const std::vector<DevNode>& tlas = built.nodes;
-    const std::vector<DevInstanceBound>& bounds = built.instance_bounds;
-    if (tlas.size() > ctx->tlas_capacity) {
-        ctx->error = "gbl_update_instances: rebuilt TLAS does not fit its reserved nodes";
-        return GBL_ERR_DEVICE;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the old TLAS
-    DevScene& sc = ctx->scene;
-    if (!inst.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstance*>(sc.instances), inst.data(), inst.size() * sizeof(DevInstance), hipMemcpyHostToDevice));
-    if (!bounds.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstanceBound*>(sc.instance_bounds), bounds.data(), bounds.size() * sizeof(DevInstanceBound), hipMemcpyHostToDevice));
-    if (!tlas.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevNode*>(sc.nodes) + ctx->tlas_base, tlas.data(), tlas.size() * sizeof(DevNode), hipMemcpyHostToDevice));
-    sc.tlas_root = built.root;
-    sc.stack_entries = scene_stack_entries(tlas, ctx->tlas_base, built.root, inst, ctx->mesh_stack_need);   // (the wavefront stack backing is re-checked at render time)
-    ctx->info.tlas_depth = built.depth;
-    ctx->info.tlas_nodes = tlas.size();
-    ctx->h_instances.swap(edited);
-    ctx->auto_rays_per_path.clear();   // the edited scene's paths may be longer or shorter: AUTO measures again
-    return GBL_OK;
+    return rebuild_tlas(ctx, edited, "gbl_update_instances");
 }
 gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
     return gbl_guard([&] { return gbl_update_instances_impl(ctx, first, count, to_world); }, [&](const std::string& what) { if (ctx) ctx->error = what; });

@@ -1,5 +1,5 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
-// api_film.hip, api_motion.hip) share.  No kernel header is needed to read it.
+// api_film.hip, api_motion.hip, api_geometry.hip) share.  No kernel header is needed to read it.
 #pragma once
 #include <string>
 
@@ -15,6 +15,12 @@ gbl_status device_alloc(gbl_ctx* ctx, size_t bytes, const char* what, void** out
 
 // Grow a device buffer of the context to at least `bytes`; what it held is not kept (api_context.hip)
 gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what);
+
+// The tail instance edits and vertex edits share: the instance records, instance bounds and TLAS over `instances` (build_tlas
+// with the context's mesh bounds and roots), uploaded into their reserved regions behind a device synchronisation; then
+// stack_entries, gbl_info's TLAS fields, the AUTO pilot's reset, and `instances` becomes the context's own.  `who` starts the
+// error messages.  A refusal (build_tlas's, or a TLAS beyond the reserved nodes) leaves the context untouched.  (api_context.hip)
+gbl_status rebuild_tlas(gbl_ctx* ctx, std::vector<gbl_instance>& instances, const char* who);
 
 // A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it first
 template <class K>

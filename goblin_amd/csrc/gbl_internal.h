@@ -17,6 +17,7 @@
 #include "kernels/denoise_args.h"
 #include "kernels/temporal_args.h"
 #include "kernels/motion_args.h"
+#include "kernels/refit_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -83,6 +84,20 @@ struct gbl_ctx {
     int blas_depth = 0;
     std::vector<int> mesh_stack_need;   // scene_prep.h PackedScene::mesh_stack_need
     bool has_directional = false;
+    // what gbl_update_vertices needs to refit a mesh's BLAS (api_geometry.hip)
+    std::vector<float> h_positions;          // 3 per vertex: gbl_create's at first, the edited ones after (gbl_get_vertices)
+    std::vector<uint32_t> h_indices;         // 3 per triangle, mesh-local
+    std::vector<uint32_t> mesh_tri_first;    // per mesh: its first record of `tris` (triangle meshes; either builder)
+    std::vector<unsigned char> mesh_emits;   // per mesh: an area light emits from it
+    uint64_t num_nodes = 0;                  // records of the node array
+    std::vector<DevNode> h_nodes;            // the node array as downloaded at the first vertex edit: the plans read its child references
+    struct MeshRefit {
+        bool built = false;
+        std::vector<uint32_t> level_first;   // scene_refit.h RefitPlan::level_first
+        RefitRecord* plan = nullptr;         // device: the plan's records ...
+        RefitBox* node_box = nullptr;        // ... and a box per record
+    };
+    std::vector<MeshRefit> refit;            // per mesh, built at its first edit
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
@@ -164,6 +179,11 @@ gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext);
 void gbl_launch_temporal_accumulate_motion(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance,
                                            const float* history_in, float* history_out, float* film_out, float* variance_out, const float* motion,
                                            const TemporalArgs& a, hipStream_t stream);
+// kernels_refit.hip: the passes of gbl_update_vertices (kernels/refit.h)
+void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade* tri_shade, const float* pos, uint32_t num_vertices, uint32_t first,
+                           uint32_t count, hipStream_t stream);
+void gbl_launch_refit_level(DevNode* nodes, const DevTriBound* bounds, const RefitRecord* plan, RefitBox* node_box, uint32_t begin, uint32_t end,
+                            hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

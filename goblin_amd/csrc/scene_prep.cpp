@@ -802,7 +802,6 @@ void pack_camera(const gbl_camera& c, const gbl_film& film, DevCamera* out) {
 
 // ------------------------------------------------------------------ geometry
 namespace {
-
 // BVH::buildLinearBVH (GoblinBVH.cpp:81-151) with the EqualCount split, followed only as far as the SHAPE of the tree:
 // per triangle the root-to-leaf path, the split axes along it and its place in a multi-triangle leaf.
 void reference_order(std::vector<Prim>& it, uint32_t start, uint32_t end, uint32_t depth, uint32_t path, uint64_t axes, DevTriOrder* out) {
@@ -831,6 +830,23 @@ void reference_order(std::vector<Prim>& it, uint32_t start, uint32_t end, uint32
     reference_order(it, start, mid, depth + 1, path, axes, out);
     reference_order(it, mid, end, depth + 1, path | (1u << depth), axes, out);
 }
+}   // namespace
+
+void mesh_reference_order(const float* positions, const uint32_t* indices, uint32_t tri_count, DevTriOrder* out) {
+    for (uint32_t t = 0; t < tri_count; ++t) out[t] = DevTriOrder();
+    if (tri_count == 0) return;
+    std::vector<Prim> items = triangle_prims(MeshView{positions, nullptr, nullptr, indices}, tri_count);   // BVHPrimitiveInfo (GoblinBVH.cpp:8-14)
+    reference_order(items, 0, tri_count, 0, 0u, 0ull, out);
+}
+
+void mesh_object_bound(const float* positions, uint32_t vertex_count, float lo[3], float hi[3]) {
+    Aabb bound;
+    for (uint32_t v = 0; v < vertex_count; ++v) bound.grow(positions + 3 * static_cast<size_t>(v));
+    store_bound(bound, lo, hi);
+}
+
+namespace {
+
 // The vertex attributes used at shading time
 void pack_attributes(const gbl_scene_desc& d, PackedScene* out) {
     out->positions.assign(d.positions, d.positions + 3 * static_cast<size_t>(d.num_vertices));
@@ -847,8 +863,7 @@ void pack_tri_order_and_bounds(const gbl_scene_desc& d, PackedScene* out) {
         const gbl_mesh& gm = d.meshes[mi];
         if (gm.shape != GBL_SHAPE_MESH) continue;
         const MeshView mv = view_of(d, gm);
-        std::vector<Prim> items = triangle_prims(mv, gm.tri_count);   // BVHPrimitiveInfo (GoblinBVH.cpp:8-14)
-        reference_order(items, 0, gm.tri_count, 0, 0u, 0ull, out->tri_order.data() + gm.tri_offset);
+        mesh_reference_order(mv.P, mv.I, gm.tri_count, out->tri_order.data() + gm.tri_offset);
         for (uint32_t t = 0; t < gm.tri_count; ++t) {
             DevTriBound& b = out->tri_bounds[gm.tri_offset + t];
             memset(&b, 0, sizeof(b));

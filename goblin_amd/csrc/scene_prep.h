@@ -83,6 +83,12 @@ gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err);
 // previous transforms).  false, *err set to build_tlas's refusal for instance i, when the reference cannot invert it.
 bool pack_transform(const gbl_trs& to_world, uint32_t i, float m[12], float inv[12], std::string* err);
 
+// One mesh's DevTriOrder records (the reference's visiting order, per mesh-local triangle number) and its object bound (the
+// bound of ALL its vertices), as pack_scene makes them: gbl_update_vertices makes them again over edited positions.
+// `positions` is the mesh's first vertex, `indices` its first (mesh-local) index.
+void mesh_reference_order(const float* positions, const uint32_t* indices, uint32_t tri_count, DevTriOrder* out);
+void mesh_object_bound(const float* positions, uint32_t vertex_count, float lo[3], float hi[3]);
+
 // Traversal stack entries a scene needs (kernels/trace.h): exit marker + the worst root-to-leaf sum over the TLAS nodes
 // (tlas[0..] are the nodes at absolute indices tlas_base + i) of (children - 1), + per instance its sentinel and what its
 // mesh's BLAS needs, + one spare.

@@ -91,6 +91,51 @@ class HipPathTracer:
             raise _abi.GoblinError(st, "gbl_get_instances")
         return [(tuple(arr[i].position), tuple(arr[i].orientation), tuple(arr[i].scale)) for i in range(n)]
 
+    def update_vertices(self, mesh, positions, normals=None, first=0):
+        """Give vertices first.. of triangle mesh ``mesh`` (its index in the scene's meshes) new object-space positions -- an (n, 3)
+        float32 array -- and, with ``normals``, new vertex normals; the mesh's BLAS is refitted on the device in place
+        (gbl_update_vertices).  The topology stays; without ``normals`` the vertex normals stay as they were."""
+        pos = np.ascontiguousarray(positions, np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("positions must have shape (n, 3), got %s" % (pos.shape,))
+        nrm = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, np.float32)
+            if nrm.shape != pos.shape:
+                raise ValueError("normals must have the positions' shape %s, got %s" % (pos.shape, nrm.shape))
+        st = self.lib.gbl_update_vertices(self.handle, int(mesh), int(first), pos.shape[0], pos.ctypes.data, nrm.ctypes.data if nrm is not None else None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        self.lib.gbl_get_info(self.handle, C.byref(self.info))
+
+    def vertices(self, mesh):
+        """The positions the context holds now for triangle mesh ``mesh`` (gbl_get_vertices): (vertex_count, 3) float32 -- the
+        scene's at first, the edited ones after ``update_vertices``."""
+        n = int(self.scene.desc.meshes[int(mesh)].vertex_count) if 0 <= int(mesh) < self.scene.desc.num_meshes else 0
+        out = np.empty((n, 3), np.float32)
+        st = self.lib.gbl_get_vertices(self.handle, int(mesh), 0, n, out.ctypes.data)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, "gbl_get_vertices")
+        return out
+
+    _GEOMETRY = (np.dtype([("o", "<f4", 3), ("scale", "<f4", 3), ("qlo", "<u4", 3), ("qhi", "<u4", 3), ("child", "<i4", 4)]),
+                 np.dtype([("p0", "<f4", 3), ("shade", "<u4"), ("e1", "<f4", 3), ("flags", "<u4"), ("e2", "<f4", 3), ("pad1", "<f4")]),
+                 np.dtype([("lo", "<f4", 3), ("hi", "<f4", 3), ("pad", "<f4", 2)]),
+                 np.dtype([("path", "<u4"), ("axes_lo", "<u4"), ("axes_hi", "<u4"), ("depth_rank", "<u4")]), np.dtype("<i4"))
+
+    def _geometry(self, table):
+        """A device geometry table read back (gbl_selftest_geometry) as a numpy structured array: 0 or "nodes", 1 or "tris",
+        2 or "tri_bounds", 3 or "tri_order"; 4 or "mesh_root": the BLAS root reference per mesh, as int32.  For tests."""
+        t = {"nodes": 0, "tris": 1, "tri_bounds": 2, "tri_order": 3, "mesh_root": 4}.get(table, table)
+        total = C.c_uint64()
+        st = self.lib.gbl_selftest_geometry(self.handle, t, 0, 0, None, C.byref(total))
+        if st == _abi.GBL_OK:
+            out = np.zeros(total.value, self._GEOMETRY[t])
+            st = self.lib.gbl_selftest_geometry(self.handle, t, 0, total.value, out.ctypes.data, None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return out
+
     def camera(self):
         """The camera description last set (gbl_get_camera): a gbl_camera, the scene's at first."""
         cam = _abi.gbl_camera()

@@ -693,6 +693,35 @@ gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, co
  * context holds no frame state.  GBL_ERR_INVALID for a NULL argument or a range out of bounds. */
 gbl_status gbl_get_instances(const gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_trs* out);
 
+/* Vertex edit: give vertices [first, first + count) of triangle mesh `mesh` (gbl_scene_desc::meshes index; vertex numbers are the
+ * mesh's own, 0 .. vertex_count) new object-space positions, and new normals if `normals` is not NULL.  The mesh's BLAS is
+ * refitted on the device in place; nothing is rebuilt on the host but the TLAS.
+ *  - The topology is kept: indices, triangle count, the tree's shape, the leaves' contents and every reference.  Only values
+ *    derived from positions are computed again: the triangles' p0 / e1 / e2 and bounds, the nodes' quantised child boxes, the
+ *    reference's visiting order (what exact ties are broken by), the mesh's object bound, the instance bounds and the TLAS.
+ *  - After the call every table the kernels read is what it would be for the edited positions over the same tree, and a render
+ *    equals, bit for bit, that of a context created from the edited scene.  A tree refitted after a large deformation is valid
+ *    but slower to trace than a new one: re-create the context to rebuild it.
+ *  - The call synchronises the device, as gbl_update_instances does, and GBL_SCHEDULE_AUTO measures its rays per path again.
+ *  - normals == NULL: the mesh's vertex normals stay as they were.  The caller owns that choice.
+ *  - gbl_render_motion goes on treating vertices as static: its planes follow cameras and instances only.
+ * GBL_ERR_INVALID, the context untouched: a NULL ctx or positions, a mesh index out of range or a mesh that is a sphere or a
+ * disk, a vertex range out of bounds, a non-finite coordinate, normals given for a mesh without has_normal.
+ * GBL_ERR_UNSUPPORTED, the context untouched: a mesh an area light emits from (its emitting triangles, area distribution and
+ * power would have to follow), and scenes with a directional or image based light, whose power and sampling sphere depend on
+ * the scene bound -- what gbl_update_instances refuses for the same reason.  (A participating medium needs no refusal: the
+ * scene bound it carries is read by those two kinds of light only.)  positions and normals are host pointers. */
+gbl_status gbl_update_vertices(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count,
+                               const float* positions /* host, 3 * count */, const float* normals /* host, 3 * count, or NULL */);
+/* The positions the context holds now (gbl_create's at first).  Host only, like gbl_get_instances.  GBL_ERR_INVALID for a NULL
+ * argument, a mesh out of range or not a triangle mesh, a range out of bounds. */
+gbl_status gbl_get_vertices(const gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* positions_out);
+/* Self-test hook: copy records [first, first + count) of a device geometry table to host memory; *total receives the table's
+ * record count.  table: 0 nodes (DevNode, 64 B), 1 tris (DevTri, 48 B), 2 tri_bounds (DevTriBound, 32 B), 3 tri_order (16 B).
+ * A fifth table, 4 mesh_root (int32, 4 B per mesh of the scene: the BLAS root reference an instance of the mesh carries),
+ * is the context's host copy.  out may be NULL when count is 0.  Synchronises the device. */
+gbl_status gbl_selftest_geometry(gbl_ctx* ctx, int table, uint64_t first, uint64_t count, void* out, uint64_t* total);
+
 /* Camera edit: every later call on the context sees `camera`; film and resolution stay the context's.  Host work only (the
  * scene is neither rebuilt nor uploaded) and no device synchronisation: every kernel receives the camera by value, so work
  * already queued keeps the old one.  A thin lens or an orthographic camera switches the calls to the kernels that know them,
