@@ -1,5 +1,8 @@
 // Device-resident scene layout (HBM) shared by the host packer (scene_prep.cpp)
 // and the kernels.  Everything is POD and sized/aligned for 16-byte vector loads.
+// (One exception, left as it is: the texel pool packs the image pyramids back to back, so a 4-channel pyramid behind a
+// 1-channel one starts at an offset that is no multiple of 4 floats and image_texel's float4 load is 4-byte aligned only.
+// Global loads take that; the imagetex and bumpy scenes and the slot chart of tests/texture_chart.py run it.)
 //
 //   nodes[]      64 B  4-wide BVH node, 8-bit quantised child boxes (one fetch = four
 //                      box tests).  BLAS nodes of every mesh first, then the TLAS

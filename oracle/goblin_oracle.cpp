@@ -3536,6 +3536,43 @@ int32_t orc_intersect(const orc_scene* s, const float o[3], const float d[3], fl
     out[11] = static_cast<float>(h.instance);
     return 1;
 }
+// The first-hit record of n camera samples {image_x, image_y, lens_u1, lens_u2, ...} (`dims` floats apart), in the layout of
+// gbl_aov_sample: {albedo(3), t, normal(3), instance (int32 bits), position(3), hit (uint32 bits)}; a miss is zeros with t = -1
+// and instance = -1.  The steps are PathTracer::Li's for the camera ray (path_li above): generateRay with differentials, the
+// unfiltered closest hit plus perturb (scene_intersect), computeUVDifferential, then the lookups of the bounce-0 BSDF
+// (resolve_hit_material).  The albedo is the resolved material's first colour slot: Kd / Kg / Kr in color, a subsurface material's
+// Kr in color3; for a mask resolve_hit_material already hands back the material it wraps.
+int32_t orc_first_hit(const orc_scene* s, const float* samples, int32_t dims, int64_t n, float* out) {
+    if (!s || !samples || !out || dims < 4) return -1;
+    Counters cnt;
+    for (int64_t i = 0; i < n; ++i) {
+        const float* rec = samples + static_cast<size_t>(i) * dims;
+        float* o = out + 12 * static_cast<size_t>(i);
+        RayDiff rd;
+        Ray ray = camera_ray(s, rec[0], rec[1], rec[2], rec[3], &rd);
+        Hit hit;
+        hit.frag.n = V3(0, 0, 0);
+        hit.frag.dpdv = V3(0, 0, 0);
+        int32_t inst = -1;
+        uint32_t got = 0u;
+        for (int k = 0; k < 12; ++k) o[k] = 0.0f;
+        o[3] = -1.0f;
+        if (scene_intersect(s, ray, &hit, &cnt)) {
+            compute_uv_differential(&hit.frag, &rd);
+            const ResolvedMat mat = resolve_hit_material(s, s->instances[hit.instance].material, hit.frag);
+            const float* c = mat.m.type == GBL_MAT_SUBSURFACE ? mat.m.color3 : mat.m.color;
+            o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+            o[3] = ray.maxt;
+            o[4] = hit.frag.n.x; o[5] = hit.frag.n.y; o[6] = hit.frag.n.z;
+            o[8] = hit.frag.p.x; o[9] = hit.frag.p.y; o[10] = hit.frag.p.z;
+            inst = hit.instance;
+            got = 1u;
+        }
+        memcpy(o + 7, &inst, 4);
+        memcpy(o + 11, &got, 4);
+    }
+    return 0;
+}
 int32_t orc_occluded(const orc_scene* s, const float o[3], const float d[3], float mint, float maxt) {
     Ray r;
     r.o = V3(o[0], o[1], o[2]); r.d = V3(d[0], d[1], d[2]); r.mint = mint; r.maxt = maxt < 0 ? INF : maxt;

@@ -20,6 +20,9 @@
 //   kat   <scene.json> <prefix>              known-answer tables (camera rays,
 //                                            filter table, transforms, lights)
 //   time  <scene.json> [threads]             render only, print seconds
+//   firsthit <scene.json> <samples.f32> <out.f32>
+//                                            the camera hit of given camera
+//                                            samples: bsdf(n, n), t, n, p
 // Outputs: <prefix>.film.f32 (W*H*4: r,g,b,weight), <prefix>.samples.f32,
 //          <prefix>.li.f32, <prefix>.kat.txt, and a one-line JSON on stdout.
 #include <unistd.h>
@@ -220,6 +223,45 @@ void kat(RenderContext* ctx, const std::string& prefix) {
     fclose(f);
 }
 
+// The camera hit of n camera samples {imageX, imageY, lensU1, lensU2}, by the public steps PathTracer::Li takes before its first
+// BSDF evaluation (GoblinPathtracer.cpp:58-98): generateRay, Scene::intersect, computeUVDifferential, then
+// getMaterial()->bsdf(fragment, n, n) -- for a Lambert that is Kd's lookup times INV_PI (GoblinMaterial.cpp:437-445).
+// Per sample 12 floats: {bsdf rgb, t, normal(3), 1 if the material is a LambertMaterial, position(3), 1 if hit}; a miss is
+// zeros with t = -1.
+int first_hit(const ScenePtr& scene, const char* samples_path, const char* out_path) {
+    FILE* f = fopen(samples_path, "rb");
+    if (!f) return -1;
+    fseek(f, 0, SEEK_END);
+    const size_t n = static_cast<size_t>(ftell(f)) / (4 * sizeof(float));
+    fseek(f, 0, SEEK_SET);
+    std::vector<float> in(4 * n), out(12 * n, 0.0f);
+    if (fread(in.data(), sizeof(float), in.size(), f) != in.size()) return -1;
+    fclose(f);
+    const CameraPtr cam = scene->getCamera();
+    for (size_t i = 0; i < n; ++i) {
+        Sample s;
+        s.imageX = in[4 * i], s.imageY = in[4 * i + 1], s.lensU1 = in[4 * i + 2], s.lensU2 = in[4 * i + 3];
+        RayDifferential ray;
+        cam->generateRay(s, &ray);
+        float* o = out.data() + 12 * i;
+        o[3] = -1.0f;
+        float eps = 0.0f;
+        Intersection isect;
+        if (!scene->intersect(ray, &eps, &isect)) continue;
+        isect.computeUVDifferential(ray);
+        const Fragment& fr = isect.fragment;
+        const Vector3 nrm = fr.getNormal(), p = fr.getPosition();
+        const MaterialPtr& m = isect.getMaterial();
+        const Color c = m->bsdf(fr, nrm, nrm);
+        o[0] = c.r, o[1] = c.g, o[2] = c.b, o[3] = ray.maxt;
+        o[4] = nrm.x, o[5] = nrm.y, o[6] = nrm.z;
+        o[7] = dynamic_cast<const LambertMaterial*>(m.get()) != nullptr ? 1.0f : 0.0f;
+        o[8] = p.x, o[9] = p.y, o[10] = p.z, o[11] = 1.0f;
+    }
+    write_f32(out_path, out);
+    return static_cast<int>(n);
+}
+
 }  // namespace
 
 // image <in.f32> <w> <h> <prefix> <bloom radius> <bloom weight>: the reference's image output path on a given float4 image
@@ -345,6 +387,15 @@ int main(int argc, char** argv) {
         kat(ctx, argv[3]);
         fprintf(real_stdout, "{\"mode\": \"kat\"}\n");
         return 0;
+    }
+
+    if (mode == "firsthit") {   // firsthit <scene.json> <samples.f32> <out.f32>
+        if (argc < 5) return 2;
+        int n = first_hit(scene, argv[3], argv[4]);
+        if (n < 0) return 1;
+        fprintf(real_stdout, "{\"mode\": \"firsthit\", \"n\": %d}\n", n);
+        fflush(real_stdout);
+        _exit(0);
     }
 
     int threads = 1;

@@ -182,12 +182,36 @@ def parse_kat(path):
     return out
 
 
+def make_firsthit(only, tmp):
+    """firsthit_<case>.npz: the compiled reference's camera hits (ref_harness firsthit) of every fifth camera sample of the
+    native sampler's stream, for the cases of tests/texture_chart.py FIRSTHIT_CASES: `samples` (n, 4) and `records` (n, 12)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import aov_reference as ar
+    import texture_chart as tc
+    for name in tc.FIRSTHIT_CASES:
+        if only and "firsthit_" + name not in only:
+            continue
+        d, directory, not_bilinear, _ = tc.firsthit_case(name)
+        ref = ar.Reference(gs.load_scene_text(json.dumps(d), directory), seed=tc.FIRSTHIT_SEED)
+        samples = np.ascontiguousarray(ref.samples[::tc.FIRSTHIT_STRIDE, :4])
+        jp, ip, op = (os.path.join(tmp, "firsthit_" + name + ext) for ext in (".json", ".in.f32", ".out.f32"))
+        with open(jp, "w") as f:
+            json.dump(tc.harness_doc(d, directory, not_bilinear), f)
+        samples.tofile(ip)
+        subprocess.check_output([HARNESS, "firsthit", jp, ip, op])
+        records = np.fromfile(op, np.float32).reshape(-1, 12)
+        assert records.shape[0] == samples.shape[0]
+        np.savez_compressed(os.path.join(HERE, "firsthit_" + name + ".npz"), samples=samples, records=records)
+        print("firsthit_" + name, records.shape[0], "samples,", int(records[:, 11].sum()), "hits")
+
+
 def main():
     if not os.path.exists(HARNESS):
         sys.exit("oracle/_ref/ref_harness is missing: run `make -C oracle ref` (needs /root/reference)")
     manifest = {}
     with tempfile.TemporaryDirectory() as tmp:
         only = set(sys.argv[1:])
+        make_firsthit(only, tmp)
         if only and os.path.exists(os.path.join(HERE, "manifest.json")):
             with open(os.path.join(HERE, "manifest.json")) as f:
                 manifest = json.load(f)

@@ -58,7 +58,9 @@ def lib():
         L.orc_camera_ray.restype = None
         L.orc_light_power.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
-        L.orc_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
+        L.orc_first_hit.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
+        L.orc_first_hit.restype = C.c_int32
+        L.orc_occluded.argtypes =[C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
         L.orc_li_replay.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_int32, C.POINTER(orc_counters)]
         L.orc_splat.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
@@ -139,6 +141,16 @@ class Oracle:
         out = np.zeros(12, np.float32)
         hit = lib().orc_intersect(self.h, _ptr(o), _ptr(d), mint, maxt, _ptr(out))
         return out if hit else None
+
+    def first_hit(self, samples):
+        """The (n, 12) float32 first-hit records (gbl_aov_sample rows) of n camera samples {image_x, image_y, lens_u1, lens_u2, ...}:
+        albedo(3), t, normal(3), instance, position(3), hit; words 7 and 11 are integers (view the rows as int32 / uint32)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        assert samples.ndim == 2 and samples.shape[1] >= 4, samples.shape
+        out = np.zeros((samples.shape[0], 12), np.float32)
+        if lib().orc_first_hit(self.h, _ptr(samples), samples.shape[1], samples.shape[0], _ptr(out)) != 0:
+            raise RuntimeError("orc_first_hit failed")
+        return out
 
     def occluded(self, o, d, mint=1e-3, maxt=-1.0):
         o = np.asarray(o, np.float32)

@@ -1,5 +1,5 @@
 """gbl_render_aov on the device: first-hit records against the oracle sample by sample (bit for bit, the project's LI_FLIP_TOL = 0
-standard), the three films against the oracle's splat of the expected values, and every layer above the kernel -- replay, windows,
+standard; the albedo too, which Oracle.first_hit looks up as the bounce-0 BSDF does), the three films against the oracle's splat of the expected values, and every layer above the kernel -- replay, windows,
 shards, accumulation, chunking, refusals, another stream, the command-line tool.  Expected values: tests/aov_reference.py."""
 import functools
 import json
@@ -18,6 +18,7 @@ import helpers
 import integration_helpers as ih
 import meshes
 import oracle_binding as ob
+import texture_chart as tc
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +26,22 @@ SEED = ar.SEED
 FILM_RELL2_TOL = 2.5e-5     # summation order (tests/test_gpu_parity.py)
 CLI = os.path.join(ih.REPO, "goblin_amd", "lib", "g_ray_hip")
 RECORD_SCENES = ["cornell", "shapes", "bumpy", "grid", "masked", "volume"]
+TEXTURED_SCENES = ["textured", "imagetex", "bumpy", "masked", "subsurface", "ibl"]   # first colour slots that are texture graphs, masks, Kr of a subsurface material
 BUILDERS = ["host", "device"]
+CHART = "chart_5x3"        # tests/texture_chart.py: every hit textured (the other charts: tests/test_gpu_texture_chart.py)
+
+
+def scene_of(name, shape=None):
+    return tc.scene(name[len("chart_"):]) if name.startswith("chart_") else ar.scene(name, **dict(shape or ()))
+
+
+def reference_of(name):
+    return tc.reference(name[len("chart_"):]) if name.startswith("chart_") else ar.reference(name)
 
 
 @functools.lru_cache(maxsize=None)
 def tracer(name, bvh="host", shape=None):
-    return HipPathTracer(ar.scene(name, **dict(shape or ())), 0, bvh=bvh)
+    return HipPathTracer(scene_of(name, shape), 0, bvh=bvh)
 
 
 class Records:
@@ -55,7 +66,7 @@ def bits(a):
 
 
 def assert_records_equal_oracle(rec, ref, what, geometry=True):
-    """hit, instance, t, position, normal: zero tolerance."""
+    """hit, instance, t, position, normal, albedo: zero tolerance."""
     assert rec.hit.shape == ref.hit.shape, what
     np.testing.assert_array_equal(rec.hit, ref.hit, err_msg=str(what))
     np.testing.assert_array_equal(bits(rec.t), bits(ref.t), err_msg=str(what))
@@ -63,6 +74,7 @@ def assert_records_equal_oracle(rec, ref, what, geometry=True):
         np.testing.assert_array_equal(rec.instance, ref.instance, err_msg=str(what))
         np.testing.assert_array_equal(bits(rec.position), bits(ref.position), err_msg=str(what))
         np.testing.assert_array_equal(bits(rec.normal), bits(ref.normal), err_msg=str(what))
+        np.testing.assert_array_equal(bits(rec.albedo), bits(ref.oracle_albedo), err_msg=str(what))
 
 
 # 1 ------------------------------------------------------------------------------------------------------------------
@@ -75,6 +87,21 @@ def test_records_equal_the_oracle_bit_for_bit(name, bvh):
     assert_records_equal_oracle(rec, ref, (name, bvh))
     miss = ref.hit == 0
     assert not rec.albedo[miss].any() and not rec.position[miss].any() and not rec.normal[miss].any()
+
+
+@pytest.mark.parametrize("mode", ["native", "replay"])
+@pytest.mark.parametrize("name", TEXTURED_SCENES)
+def test_textured_records_equal_the_oracle_bit_for_bit(name, mode):
+    """The whole record rows, albedo included, where the first colour slot is looked up: filtered checkerboards, image textures, a
+    mask's wrapped material, a subsurface material's Kr, under bump and normal maps."""
+    ref = ar.reference(name)
+    if mode == "native":
+        rec = device_records(name)
+    else:
+        rec = Records(tracer(name).render_aov(albedo=False, normal=False, depth=False, want_samples=True, replay_samples=ref.samples.copy()))
+    assert ref.hit.sum() > 0
+    assert_records_equal_oracle(rec, ref, (name, mode))
+    np.testing.assert_array_equal(rec.rows, ref.rows)
 
 
 # 2 ------------------------------------------------------------------------------------------------------------------
@@ -126,6 +153,7 @@ def test_textured_albedo():
         a = rec.albedo[on]
         print("textured: instance", inst, "samples", int(on.sum()), "albedo range", a.min(axis=0), a.max(axis=0))
         assert on.sum() > 0 and (a >= lo).all() and (a <= hi).all()
+    np.testing.assert_array_equal(bits(rec.albedo), bits(ref.oracle_albedo))
 
 
 def test_image_texture_albedo_is_finite_and_in_range():
@@ -134,6 +162,9 @@ def test_image_texture_albedo_is_finite_and_in_range():
     hit = ref.hit == 1
     assert hit.sum() > 0 and (~ref.albedo_known).sum() > 0
     assert np.isfinite(rec.albedo).all() and rec.albedo[hit].min() >= 0.0 and rec.albedo[hit].max() <= 1.0
+    np.testing.assert_array_equal(bits(rec.albedo), bits(ref.oracle_albedo))
+    textured = hit & ~ref.albedo_known
+    assert len(np.unique(ref.oracle_albedo[textured], axis=0)) > 100      # (the lookups vary: not one colour per instance)
 
 
 # 4 ------------------------------------------------------------------------------------------------------------------
@@ -148,9 +179,10 @@ def device_films(name, shard=None):
             "resolved": (depth.cpu().numpy(), coverage.cpu().numpy())}
 
 
-@pytest.mark.parametrize("name", ["cornell", "shapes"])
+@pytest.mark.parametrize("name", ["cornell", "shapes", "textured", "imagetex", CHART])
 def test_films_equal_the_oracles_splat(name):
-    want = ar.reference(name).films()
+    want = reference_of(name).films()
+    assert np.abs(want["albedo"][..., :3]).sum() > 0
     got = device_films(name)
     rels = {"albedo": helpers.rel_l2(got["albedo_n"], ob.normalize_film(want["albedo"])),
             "normal": helpers.rel_l2(got["normal_n"], ob.normalize_film(want["normal"]))}
