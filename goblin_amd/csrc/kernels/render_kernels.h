@@ -595,6 +595,7 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
     constexpr bool REPLAY = SAMPLER != GBL_SRC_NATIVE, STREAM = SAMPLER == GBL_SRC_STREAM, TIES = REPLAY || STATS || EXACT || EXT;
     constexpr bool WAVE = QUAD && SAMPLER == GBL_SRC_NATIVE && GBL_WAVE_UNITS;   // wave-owned work units (below); else the workgroup's item loop
     constexpr bool LAST_SKIP = SAMPLER == GBL_SRC_NATIVE && !STATS && !EXT;      // the capped vertex traces no ray under a delta light (below)
+    constexpr bool LAZY_DRAWS = LAST_SKIP;   // ... and draws a vertex's sample dimensions only where they are read ("shade the vertex" below)
     extern __shared__ __align__(16) unsigned char smem[];
     const int tp = GBL_TILE + 2 * sc.film.halo;
     float* tile = reinterpret_cast<float*>(smem);
@@ -971,21 +972,39 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
             float u_bsdf_c = 0.0f, u_bsdf_1 = 0.0f, u_bsdf_2 = 0.0f;
             if (vis && !finished) {
                 const int b = ps.bounce;
-                float u_light_c, u_light_1, u_light_2, u_pick;
+                // The vertex's seven sample dimensions: 1D 3b (light component), 3b + 1 (BSDF component), 3b + 2 (light pick); 2D
+                // 2b (light), 2b + 1 (BSDF).  The replay, stream, instrumented and EXT builds take all seven here, ahead of the
+                // vertex, like the reference (its records, cnt.dims).  The native sampler is counter-based -- a draw is a pure
+                // function of (pixel key, pattern, k) -- so the lean native kernels (LAZY_DRAWS) leave out the draws nobody reads
+                // and pass 0.0f instead: the pick is drawn with more than one light, the light's three by the lanes that picked a
+                // light whose light_sample reads them, and of the BSDF's three a lane draws EITHER the component OR the pair, by
+                // its material, in one instruction stream (native_1d_or_2d; shade.h says who reads what).  The BSDF's draw stays
+                // here, unconditional, on purpose: one draw per material type in branches of their own ahead of mat_sample, the
+                // form that skips most, held seven more SGPRs across the bounce loop, whose spill reads (v_readlane) landed in
+                // the closest-hit loops -- 0.9 % slower than drawing everything (profiles/lazy_draws_ab.txt).
+                float u_light_c = 0.0f, u_light_1 = 0.0f, u_light_2 = 0.0f, u_pick = 0.0f;
                 if (REPLAY) {
                     const float* r1 = src.rec + 4 + 3 * b;
                     const float* r2 = src.rec + ra.off2_base + 4 * b;
                     u_light_c = r1[0]; u_bsdf_c = r1[1]; u_pick = r1[2];
                     u_light_1 = r2[0]; u_light_2 = r2[1]; u_bsdf_1 = r2[2]; u_bsdf_2 = r2[3];
-                } else {
+                } else if constexpr (!LAZY_DRAWS) {
                     u_light_c = src.native_1d(3u * b + 0u);
                     u_bsdf_c = src.native_1d(3u * b + 1u);
                     u_pick = src.native_1d(3u * b + 2u);
                     src.native_2d(0x10000u + 2u * b, 1u, 0u, true, &u_light_1, &u_light_2);
                     src.native_2d(0x10000u + 2u * b + 1u, 1u, 0u, true, &u_bsdf_1, &u_bsdf_2);
+                } else {
+                    const bool pair = !mat_sample_reads_comp(sc.materials[sc.instances[hit.inst].material]);
+                    float a0, a1;
+                    src.native_1d_or_2d(pair, 3u * b + 1u, 0x10000u + 2u * b + 1u, &a0, &a1);
+                    u_bsdf_c = pair ? 0.0f : a0;
+                    u_bsdf_1 = pair ? a0 : 0.0f;
+                    u_bsdf_2 = pair ? a1 : 0.0f;
                 }
                 if (STATS) cnt.dims += 7;
-                // Scene::sampleLight: CDF1D::sampleDiscrete over the power distribution
+                // Scene::sampleLight: CDF1D::sampleDiscrete over the power distribution (one light: index 0 for every u)
+                if (LAZY_DRAWS && sc.num_lights > 1) u_pick = src.native_1d(3u * b + 2u);
                 int li = 0;
                 for (int i = 1; i <= sc.num_lights; ++i)
                     if (sc.light_cdf[i] < u_pick) li = i;
@@ -996,6 +1015,10 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                 mat = sc.materials + sc.instances[hit.inst].material;
                 if (EXT) resolve_hit_material(sc, sc.instances[hit.inst].material, fr, tf, rmat);
                 const DevLight& light = sc.lights[li];
+                if (LAZY_DRAWS && light_sample_reads_u<EXT>(light)) {
+                    u_light_c = src.native_1d(3u * b + 0u);
+                    src.native_2d(0x10000u + 2u * b, 1u, 0u, true, &u_light_1, &u_light_2);
+                }
                 LightSampleOut ls;
                 light_sample<EXT>(sc, light, fr.p, fr.eps, u_light_c, u_light_1, u_light_2, ls);
                 if (!is_black(ls.L) && ls.pdf > 0.0f) {

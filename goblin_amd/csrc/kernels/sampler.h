@@ -85,6 +85,29 @@ struct SampleSource {
     __device__ __forceinline__ void native_2d_slot(uint32_t pattern_id, uint32_t n, uint32_t slot, float* u, float* v) const {
         native_2d(pattern_id, n, slot_stratum(pattern_id, n, slot), true, u, v);
     }
+    // native_1d(p1) -> *u for a lane with two == false, native_2d(p2, 1, 0, true) -> (*u, *v) for a lane with two == true: the same
+    // values bit for bit, but the key, the permutation with its cycle-walk loop and the first jitter hash are one instruction
+    // stream for both kinds of lane, which differ in the operands they feed it
+    __device__ __forceinline__ void native_1d_or_2d(bool two, uint32_t p1, uint32_t p2, float* u, float* v) const {
+        uint32_t ky = key(two ? p2 : 2u + p1, 0u);
+        uint32_t j = nat_permute(k, static_cast<uint32_t>(spp), ky);
+        float h0 = nat_u01(nat_mix(ky, two ? 2u * k : k));
+        if (two) {
+            float strata = 1.0f / 1;
+            float sub = strata / root;
+            int px = static_cast<int>(j) % root, py = static_cast<int>(j) / root;
+            float xo = px + h0;
+            float yo = py + nat_u01(nat_mix(ky, 2u * k + 1u));
+            *u = 0 * strata + xo * sub;
+            *v = 0 * strata + yo * sub;
+        } else {
+            float strata = 1.0f / 1.0f;
+            float sub = strata / spp;
+            float off = j + h0;
+            *u = 0u * strata + off * sub;
+            *v = 0.0f;
+        }
+    }
     // 2D pattern: stratum i of an n-point pattern (n a perfect square), sub-cell grid root x root
     __device__ __forceinline__ void native_2d(uint32_t pattern_id, uint32_t n, uint32_t i, bool permute, float* u, float* v) const {
         uint32_t ky = key(pattern_id, i);

@@ -452,6 +452,13 @@ __device__ __forceinline__ float mat_pdf(const DevMaterial& m, F3 n, F3 wo, F3 w
     return 0.0f;
 }
 
+// Which of mat_sample's sample arguments a material type reads -- kept beside the function that does the reading.  u_comp is
+// read by the transparent material alone (its choice between reflection and refraction), and that material reads nothing else;
+// the pair (u1, u2) by the Lambert and Blinn lobes; the mirror and the subsurface material's reflection read none.  So no lane
+// reads both: a caller that draws lazily (the lean native path kernels) draws the component for the lanes this names and the
+// pair for the others, and passes 0.0f for what it did not draw.
+__device__ __forceinline__ bool mat_sample_reads_comp(const DevMaterial& m) { return m.type == GBL_MAT_TRANSPARENT; }
+
 // material->sampleBSDF(fragment, wo, bs, &wi, &pdf, BSDFAll, &sampledType); *specular = sampledType & BSDFSpecular
 __device__ __forceinline__ F3 mat_sample(const DevMaterial& m, const Frag& fr, F3 wo, float u_comp, float u1, float u2, F3* wi,
                                          float* pdf, bool* specular) {
@@ -724,6 +731,14 @@ __device__ __forceinline__ F3 light_shape_sample(const DevLight& l, F3 p, float 
     else p_hit = p + (sqrtf(d2) * cos_max) * d;   // the ray scratches over the sphere's surface
     *normal = normalize(p_hit);
     return p_hit;
+}
+
+// Whether light_sample reads its sample arguments (u_comp, u1, u2) for this light -- kept beside the function that does the
+// reading.  The area lights (triangle pick, point on it) and the image based light do; the point, spot and directional
+// branches read none of the three.  A caller that draws lazily asks this and passes 0.0f otherwise.
+template <bool EXT>
+__device__ __forceinline__ bool light_sample_reads_u(const DevLight& l) {
+    return l.type == GBL_LIGHT_AREA || (EXT && l.type == GBL_LIGHT_IBL);
 }
 
 // light->sampleL(p, epsilon, ls, ...)
