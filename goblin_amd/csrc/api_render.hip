@@ -143,6 +143,15 @@ static uint64_t medium_draws_per_sample(const DevScene& sc) {
     const double steps = std::floor(diag / std::max(1e-6, double(v.step))) + 3.0;
     return 2ull + 5ull * static_cast<uint64_t>(std::min(steps, 1.0e6)) + 700ull;
 }
+// GBL_STREAM_TAIL: the tail per sample the knob asks for, raised to the least with which stream_medium_phase can still walk a
+// pixel's S samples one per chunk.  Homogeneous: one sample's draws.  Heterogeneous: a sample's share of ONE sample's budget --
+// that budget already holds the generator state's room, which the phase takes off the pixel's whole tail, not off every
+// sample's, so S times the budget (what the knob used to be raised to) left no pixel with more than one chunk.
+static uint32_t knob_stream_tail(const DevScene& sc, uint64_t knob, uint32_t S) {
+    const uint64_t med = medium_draws_per_sample(sc);
+    const uint64_t least = sc.volume.hetero != 0u ? (med + S - 1) / std::max(1u, S) : med;
+    return static_cast<uint32_t>(std::max<uint64_t>(least, knob));
+}
 
 // Stack levels of the wavefront trace kernels beyond the LDS part: one column per thread of the largest persistent
 // trace grid (8 workgroups per CU).  Re-made when an instance edit deepens the TLAS.
@@ -732,7 +741,7 @@ gbl_status render_whitted(gbl_ctx* ctx, Plan& pl, const RenderKnobs& knobs, hipE
             const uint64_t med = medium_draws_per_sample(sc);
             const uint64_t worst = ((2ull << std::min(ra.max_depth, 20)) - 1) * (6 * slots + 6) + med;
             tail = static_cast<uint32_t>(std::max<uint64_t>(med, std::min<uint64_t>(worst, (1ull << 20) / pl.layout.S)));
-            if (knobs.stream_tail_set) tail = static_cast<uint32_t>(std::max<uint64_t>(med, knobs.stream_tail));
+            if (knobs.stream_tail_set) tail = knob_stream_tail(sc, knobs.stream_tail, pl.layout.S);
         }
         ra.stream_tail_cap = pl.layout.S * tail;
         if ((st = ensure_stream_buffers(ctx, stream_scratch_words(pl.layout, tail), grid.x, pl.entries, &ra)) != GBL_OK) return st;
@@ -838,7 +847,7 @@ gbl_status render_megakernel(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl,
         // a sample's tail in the stream: up to 6 discarded floats per bounce, 9 per light sample of the medium
         const uint32_t med = static_cast<uint32_t>(medium_draws_per_sample(sc));
         uint32_t tail_words = (ao ? 0u : 6u * static_cast<uint32_t>(ra.max_depth)) + med;
-        if (knobs.stream_tail_set && sc.volume.on) tail_words = std::max<uint32_t>(med, static_cast<uint32_t>(knobs.stream_tail));
+        if (knobs.stream_tail_set && sc.volume.on) tail_words = knob_stream_tail(sc, knobs.stream_tail, pl.layout.S);
         ra.stream_tail_cap = pl.layout.S * tail_words;
         if ((st = ensure_stream_buffers(ctx, stream_scratch_words(pl.layout, tail_words), grid64, pl.entries, &ra)) != GBL_OK) return st;
     } else {

@@ -2415,6 +2415,20 @@ struct LiCtx {
     // (goblin_amd/csrc/kernels/render_kernels.h, wavefront.h).  Native sampler only: the draw is keyed by the pixel and sample.
     bool rr = false;
     uint32_t rr_pixel_key = 0, rr_k = 0;
+    struct MediumProbe* probe = nullptr;   // orc_medium / orc_render_medium: what the medium did for the current sample
+};
+// What the medium probe notes about one camera sample (test infrastructure, tests/test_medium_chart_cpu.py).
+enum : uint32_t {
+    MEDIUM_CROSSES = 1u,        // the camera ray meets the region (Renderer::Lv's intersect)
+    MEDIUM_THIN = 2u,           // ... and took the (tmax - tmin) < 1e-5f early-out
+    MEDIUM_CLIPPED = 4u,        // Li left the camera ray's maxt finite (a surface was hit)
+    MEDIUM_ENDS_INSIDE = 8u,    // the clipped ray ends inside the region
+    MEDIUM_OCCLUDED = 16u,      // a light sample taken from a point inside the region was occluded by the scene
+    MEDIUM_UNOCCLUDED = 32u,    // ... was not
+    MEDIUM_LIGHT0 = 256u        // << k: light k (k < 8) was the picked light of a non-black term
+};
+struct MediumProbe {
+    uint32_t flags = 0, draws = 0;
 };
 inline uint32_t nat_mix(uint32_t a, uint32_t b);
 inline float nat_u01(uint32_t h);
@@ -3081,7 +3095,11 @@ struct VolRand {
         memcpy(&by, rec + 1, 4);
         key = nat_mix(bx, by);
     }
-    float f() { return c->rng ? c->rng->f() : nat_u01(nat_mix(key, 0x766f6c00u + i++)); }
+    uint32_t drawn = 0;
+    float f() {
+        ++drawn;
+        return c->rng ? c->rng->f() : nat_u01(nat_mix(key, 0x766f6c00u + i++));
+    }
 };
 inline float vol_rand_next(VolRand& rnd);
 inline bool box_intersect(const Box& b, V3 o, V3 d, float mint, float maxt, float* tmin, float* tmax) {   // BBox::intersect, GoblinBBox.cpp:57-77
@@ -3206,6 +3224,13 @@ V3 light_sample_position(const orc_scene* s, int li, float u_comp, float u1, flo
     return l.pos;
 }
 inline float vol_rand_next(VolRand& rnd) { return rnd.f(); }
+// the probe's notes (no effect on the arithmetic): a light sample's shadow query, and the light of a term that adds radiance
+inline void probe_shadow(LiCtx* c, bool inside, bool occluded) {
+    if (c->probe && inside) c->probe->flags |= occluded ? MEDIUM_OCCLUDED : MEDIUM_UNOCCLUDED;
+}
+inline void probe_term(LiCtx* c, int light, Col term) {
+    if (c->probe && light < 8 && term != BLACK) c->probe->flags |= MEDIUM_LIGHT0 << light;
+}
 // Renderer::Lv, heterogeneous branch (GoblinRenderer.cpp:397-445): march the camera ray in steps of step_size from a
 // jittered start; at every sample point one light sample (pick + LightSample: 4 random numbers, one more for the shadow
 // ray's own jittered transmittance when it is unoccluded).
@@ -3236,11 +3261,15 @@ Col volume_lv_hetero(LiCtx* c, const Ray& ray, float tmin, float tmax, VolRand& 
             Ray shadow;
             Col L = light_sample(s, light, p, 0.0f, u_comp, u1, u2, &wi, &light_pdf_v, &shadow);
             if (L != BLACK && light_pdf_v > 0.0f) {
-                if (!scene_occluded(s, shadow, &c->cnt)) {
+                const bool occluded = scene_occluded(s, shadow, &c->cnt);
+                probe_shadow(c, vol_contains(s, p), occluded);
+                if (!occluded) {
                     Col tr_light = vol_transmittance(s, shadow, rnd);
                     Col Ld = tr_light * L / (pick_pdf * light_pdf_v);
                     float phase = vol_contains(s, p) ? phase_hg(ray.d, wi, vol.g) : 0.0f;   // VolumeRegion::phase
-                    Lv += transmittance * sigma_s * phase * Ld;
+                    Col term = transmittance * sigma_s * phase * Ld;
+                    probe_term(c, light, term);
+                    Lv += term;
                 }
             }
         }
@@ -3284,14 +3313,18 @@ Col volume_lv(LiCtx* c, const Ray& ray, VolRand& rnd) {
             Ray shadow;
             Col Le = light_sample(s, light, p_e, 0.0f, e_comp, e_u1, e_u2, &wi, &light_pdf_v, &shadow);
             if (Le != BLACK && light_pdf_v > 0.0f) {
-                if (!scene_occluded(s, shadow, &c->cnt)) {
+                const bool occluded = scene_occluded(s, shadow, &c->cnt);
+                probe_shadow(c, in_e, occluded);
+                if (!occluded) {
                     Col tr_light = vol_transmittance(s, shadow, rnd);
                     Col Ld = tr_light * Le / (pick_pdf * light_pdf_v);
                     float phase = in_e ? phase_hg(ray.d, wi, vol.g) : 0.0f;   // VolumeRegion::phase(p, wi, wo), GoblinVolume.cpp:17-23
                     float sig = luminance(sigma_te);
                     float pdf_td = sig / (std::exp(sig * (te - a)) - std::exp(sig * (te - b)));   // exponentialPdf(t, sigma, a, b)
                     float mis = power_heuristic(1, pdf_te, 1, pdf_td);
-                    Lv += mis * tr_e * scatter_e * phase * Ld / pdf_te;
+                    Col term = mis * tr_e * scatter_e * phase * Ld / pdf_te;
+                    probe_term(c, light, term);
+                    Lv += term;
                 }
             }
         }
@@ -3312,13 +3345,17 @@ Col volume_lv(LiCtx* c, const Ray& ray, VolRand& rnd) {
             Ray shadow;
             Col Ldist = light_sample(s, light, p_d, 0.0f, d_comp, d_u1, d_u2, &wi, &light_pdf_v, &shadow);
             if (Ldist != BLACK && light_pdf_v > 0.0f) {
-                if (!scene_occluded(s, shadow, &c->cnt)) {
+                const bool occluded = scene_occluded(s, shadow, &c->cnt);
+                probe_shadow(c, in_d, occluded);
+                if (!occluded) {
                     Col tr_light = vol_transmittance(s, shadow, rnd);
                     Col Ld = tr_light * Ldist / (pick_pdf * light_pdf_v);
                     float phase = in_d ? phase_hg(ray.d, wi, vol.g) : 0.0f;
                     float pdf_te2 = D / ((theta_b - theta_a) * (D * D + td * td));
                     float mis = power_heuristic(1, pdf_td, 1, pdf_te2);
-                    Lv += mis * tr_d * scatter_d * phase * Ld / pdf_td;
+                    Col term = mis * tr_d * scatter_d * phase * Ld / pdf_td;
+                    probe_term(c, light, term);
+                    Lv += term;
                 }
             }
         }
@@ -3326,14 +3363,38 @@ Col volume_lv(LiCtx* c, const Ray& ray, VolRand& rnd) {
     return Lv / static_cast<float>(n_samples);
 }
 // what RenderTask::run adds to the tile for one camera sample: w * (tr * L + Lv), w = 1
-inline Col task_sample(LiCtx* c, const float* rec, Col L) {
+// The medium's two terms for one camera sample, after Li has left the camera ray's maxt in c->primary_maxt.  With c->probe set
+// it also notes what happened on the way (orc_medium below).
+inline void medium_terms(LiCtx* c, const float* rec, Col* tr, Col* Lv) {
+    Ray ray = camera_ray(c->s, rec[0], rec[1], rec[2], rec[3], nullptr);
+    ray.maxt = c->primary_maxt;
+    VolRand rnd(c, rec);
+    *tr = vol_transmittance(c->s, ray, rnd);   // Renderer::transmittance: the homogeneous region draws nothing, the heterogeneous one its jitter
+    *Lv = volume_lv(c, ray, rnd);
+    if (c->probe) {
+        float tmin, tmax;
+        c->probe->draws = rnd.drawn;
+        if (ray.maxt < INF) c->probe->flags |= MEDIUM_CLIPPED;
+        if (vol_intersect(c->s, ray, &tmin, &tmax)) {
+            c->probe->flags |= MEDIUM_CROSSES;
+            if ((tmax - tmin) < 1e-5f) c->probe->flags |= MEDIUM_THIN;
+            if (ray.maxt < INF && tmax == ray.maxt) c->probe->flags |= MEDIUM_ENDS_INSIDE;   // BBox::intersect starts from [mint, maxt]
+        }
+    }
+}
+inline Col task_sample(LiCtx* c, const float* rec, Col L, float* medium_out = nullptr) {
     Col tr(1.0f), Lv(BLACK);
     if (c->s->volume.on) {
-        Ray ray = camera_ray(c->s, rec[0], rec[1], rec[2], rec[3], nullptr);
-        ray.maxt = c->primary_maxt;
-        VolRand rnd(c, rec);
-        tr = vol_transmittance(c->s, ray, rnd);   // Renderer::transmittance: the homogeneous region draws nothing, the heterogeneous one its jitter
-        Lv = volume_lv(c, ray, rnd);
+        MediumProbe probe;
+        c->probe = medium_out ? &probe : nullptr;
+        medium_terms(c, rec, &tr, &Lv);
+        c->probe = nullptr;
+        if (medium_out) {
+            medium_out[0] = tr.r; medium_out[1] = tr.g; medium_out[2] = tr.b;
+            medium_out[3] = Lv.r; medium_out[4] = Lv.g; medium_out[5] = Lv.b;
+            medium_out[6] = static_cast<float>(probe.draws);
+            medium_out[7] = static_cast<float>(probe.flags);
+        }
     }
     Col TL = tr * L;
     Col out(TL.r + Lv.r, TL.g + Lv.g, TL.b + Lv.b, TL.a);
@@ -3617,6 +3678,22 @@ int32_t orc_li_replay(const orc_scene* s, const gbl_render_setting* rs, const fl
     return 0;
 }
 
+// The medium probe: per record {tr rgb, Lv rgb, number of medium draws, MEDIUM_* flags} -- the very terms orc_li_replay folds
+// into its output (task_sample), under the same hashed draws.  Li runs first because it is what clips the camera ray.
+int32_t orc_medium(const orc_scene* s, const gbl_render_setting* rs, const float* samples, int64_t n, float* out) {
+    if (!s || !rs || !samples || !out || !s->volume.on) return -1;
+    PtIndices ix;
+    Quota q = make_quota(*rs, &ix, s);
+    const uint32_t dims = q.dims();
+    LiCtx c;
+    c.s = s; c.rs = rs; c.q = &q; c.ix = &ix; c.rng = nullptr; c.ref_faithful = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        Col L = eval_li(&c, samples + i * dims);
+        task_sample(&c, samples + i * dims, L, out + 8 * i);
+    }
+    return 0;
+}
+
 // Debugging aid: every scene query the Li evaluation of ONE record issues (see Counters::log); returns the count.
 int32_t orc_debug_rays(const orc_scene* s, const gbl_render_setting* rs, const float* rec, float* out, int32_t max_rays) {
     PtIndices ix;
@@ -3702,9 +3779,12 @@ int32_t orc_li_native(const orc_scene* s, const gbl_render_setting* rs, uint64_t
 // per-thread ImageTile + mergeTile).
 //   samples_out / li_out: optional, all records in tile-then-pixel order.
 //   sampler: 0 = reference stream (mt19937), 1 = native counter-based law.
-int32_t orc_render(const orc_scene* s, const gbl_render_setting* rs, int32_t threads, int32_t ref_faithful, int32_t sampler,
-                   uint64_t seed, float* film_accum, float* samples_out, float* li_out, double* seconds,
-                   orc_counters* counters) {
+//   medium_out: optional (orc_render_medium), the medium probe's 8 floats per record under this render's own draws; with it
+//               li_out receives Li itself, as the reference's probes log it, not tr * L + Lv.
+}  // extern "C"
+static int32_t render_impl(const orc_scene* s, const gbl_render_setting* rs, int32_t threads, int32_t ref_faithful, int32_t sampler,
+                           uint64_t seed, float* film_accum, float* samples_out, float* li_out, float* medium_out, double* seconds,
+                           orc_counters* counters) {
     PtIndices ix;
     Quota q = make_quota(*rs, &ix, s);
     uint32_t dims = q.dims();
@@ -3762,9 +3842,9 @@ int32_t orc_render(const orc_scene* s, const gbl_render_setting* rs, int32_t thr
                     for (int k = 0; k < spp; ++k) {
                         const float* rec = recs.data() + static_cast<size_t>(k) * dims;
                         Col L = eval_li(&c, rec);
-                        Col out = task_sample(&c, rec, L);   // RenderTask::run: w * (tr * L + Lv)
+                        Col out = task_sample(&c, rec, L, medium_out ? medium_out + rec_index * 8 : nullptr);   // RenderTask::run: w * (tr * L + Lv)
                         add_sample(s, film, rec[0], rec[1], out, &splats[tid]);
-                        if (s->volume.on) L = out;           // with a medium the per-sample output is what the tile receives
+                        if (s->volume.on && !medium_out) L = out;   // with a medium the per-sample output is what the tile receives
                         if (samples_out) memcpy(samples_out + rec_index * dims, rec, dims * sizeof(float));
                         if (li_out) {
                             li_out[4 * rec_index] = L.r; li_out[4 * rec_index + 1] = L.g;
@@ -3796,6 +3876,18 @@ int32_t orc_render(const orc_scene* s, const gbl_render_setting* rs, int32_t thr
         }
     }
     return 0;
+}
+
+extern "C" {
+int32_t orc_render(const orc_scene* s, const gbl_render_setting* rs, int32_t threads, int32_t ref_faithful, int32_t sampler,
+                   uint64_t seed, float* film_accum, float* samples_out, float* li_out, double* seconds,
+                   orc_counters* counters) {
+    return render_impl(s, rs, threads, ref_faithful, sampler, seed, film_accum, samples_out, li_out, nullptr, seconds, counters);
+}
+int32_t orc_render_medium(const orc_scene* s, const gbl_render_setting* rs, int32_t sampler, uint64_t seed, float* film_accum,
+                          float* samples_out, float* li_out, float* medium_out) {
+    if (!s || !s->volume.on || !medium_out) return -1;
+    return render_impl(s, rs, 1, 0, sampler, seed, film_accum, samples_out, li_out, medium_out, nullptr, nullptr);
 }
 
 // MIPMap<T>::lookup of image `image` of the scene for n queries {s, t, dsdx, dtdx, dsdy, dtdy} -> n x {r, g, b, a}

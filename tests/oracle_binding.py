@@ -71,6 +71,11 @@ def lib():
         L.orc_render.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_int32, C.c_int32, C.c_int32,
                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                                  C.POINTER(orc_counters)]
+        L.orc_medium.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_void_p, C.c_int64, C.c_void_p]
+        L.orc_medium.restype = C.c_int32
+        L.orc_render_medium.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+        L.orc_render_medium.restype = C.c_int32
         L.orc_hardware_threads.restype = C.c_int32
         L.orc_mip_lookup.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
         L.orc_mip_lookup.restype = C.c_int32
@@ -167,6 +172,33 @@ class Oracle:
         cnt = orc_counters()
         lib().orc_li_replay(self.h, C.byref(s), _ptr(samples), n, _ptr(li), threads, C.byref(cnt))
         return li, cnt.as_dict()
+
+    # the medium probe's flags (word 7 of a record, an integer)
+    MEDIUM_CROSSES, MEDIUM_THIN, MEDIUM_CLIPPED, MEDIUM_ENDS_INSIDE, MEDIUM_OCCLUDED, MEDIUM_UNOCCLUDED, MEDIUM_LIGHT0 = 1, 2, 4, 8, 16, 32, 256
+
+    def medium(self, samples, setting=None):
+        """The medium's part of li_replay, per record (n, 8): {tr rgb, Lv rgb, number of medium draws, flags} under the hashed draws
+        of the replay and native samplers.  li_replay's output is float32(tr * L + Lv) with L the same replay without the medium."""
+        s = setting or self.scene.desc.setting
+        samples = np.ascontiguousarray(samples, np.float32)
+        assert samples.shape[1] == self.dims(s), (samples.shape, self.dims(s))
+        out = np.zeros((samples.shape[0], 8), np.float32)
+        if lib().orc_medium(self.h, C.byref(s), _ptr(samples), samples.shape[0], _ptr(out)) != 0:
+            raise RuntimeError("orc_medium failed (no medium in the scene?)")
+        return out
+
+    def render_medium(self, setting=None, sampler=0, seed=0):
+        """render(threads=1) with the probe along: dict(film, samples, li, medium) in tile-then-pixel order, where `li` is Li itself
+        (what the compiled reference's probes log) and `medium` the probe's records under this render's own draws."""
+        s = setting or self.scene.desc.setting
+        d = self.scene.desc
+        film = np.zeros((d.film.yres, d.film.xres, 4), np.float32)
+        w = self.window()
+        n = (w[1] - w[0]) * (w[3] - w[2]) * int(np.ceil(np.sqrt(np.float32(s.sample_per_pixel)))) ** 2
+        samples, li, medium = np.zeros((n, self.dims(s)), np.float32), np.zeros((n, 4), np.float32), np.zeros((n, 8), np.float32)
+        if lib().orc_render_medium(self.h, C.byref(s), sampler, seed, _ptr(film), _ptr(samples), _ptr(li), _ptr(medium)) != 0:
+            raise RuntimeError("orc_render_medium failed (no medium in the scene?)")
+        return {"film": film, "samples": samples, "li": li, "medium": medium}
 
     def splat(self, samples, li, film=None):
         d = self.scene.desc
