@@ -2416,7 +2416,32 @@ struct LiCtx {
     bool rr = false;
     uint32_t rr_pixel_key = 0, rr_k = 0;
     struct MediumProbe* probe = nullptr;   // orc_medium / orc_render_medium: what the medium did for the current sample
+    struct SssProbe* sss = nullptr;        // orc_subsurface: what Lsubsurface did for the current sample
+    int sss_level = 0;                     // the recursion level of the Lsubsurface call under way (Whitted; 0 elsewhere)
 };
+// What the subsurface probe notes about one camera sample (test infrastructure, tests/test_sss_chart_cpu.py): the two terms of
+// the sample's first Lsubsurface evaluation, and counters over the slots of all of them (Whitted evaluates it at every level).
+enum {
+    SSS_SINGLE = 0, SSS_MULTI = 3,                      // rgb each, of the first evaluation
+    SSS_CALLS = 6, SSS_CALLS_DEEP = 7,                  // evaluations; those at a recursion level > 0
+    SSS_AXIS_N = 8, SSS_AXIS_U = 9, SSS_AXIS_V = 10,    // slots by probe axis
+    SSS_PROBE_MISS = 11, SSS_PROBE_OTHER = 12,          // the probe ray hit nothing / a surface of another material
+    SSS_PROBE_BLACK = 13, SSS_PROBE_OCCLUDED = 14, SSS_PROBE_ACCEPTED = 15,   // it hit the same material: light sample black / shadowed / added
+    SSS_SINGLE_BLACK = 16, SSS_SINGLE_MISS = 17, SSS_SINGLE_OTHER = 18, SSS_SINGLE_OCCLUDED = 19, SSS_SINGLE_ACCEPTED = 20,
+    SSS_LIGHTS = 21,                                    // bit k: light k (k < 16) was picked by some slot
+    SSS_NAN = 22,                                       // 1: NaN in a single term, 2: in a multi term (any evaluation)
+    SSS_FIRST_LEVEL = 23,                               // the first evaluation's recursion level
+    SSS_MI_DIFFERS = 24, SSS_MP_DIFFERS = 25,           // slots whose exit / probe fragment resolved other coefficients than `frag` did
+    SSS_MAX_LEVEL = 26,                                 // the deepest evaluation's recursion level
+    SSS_PROBE_WORDS = 28
+};
+struct SssProbe {
+    float w[SSS_PROBE_WORDS] = {};
+    uint32_t lights = 0, nan = 0;
+};
+inline void sss_note(LiCtx* c, int word) {
+    if (c->sss) c->sss->w[word] += 1.0f;
+}
 // What the medium probe notes about one camera sample (test infrastructure, tests/test_medium_chart_cpu.py).
 enum : uint32_t {
     MEDIUM_CROSSES = 1u,        // the camera ray meets the region (Renderer::Lv's intersect)
@@ -2644,11 +2669,15 @@ Col l_bssrdf_single(LiCtx* c, const Frag& frag, uint32_t material, V3 wo, const 
         float sample_pdf = falloff * std::exp(-falloff * d);   // exponentialPdf, :223-225
         float pick_pdf;
         int light = s->light_power.sample_discrete(bs.pick_light, &pick_pdf);
+        if (c->sss && light >= 0 && light < 16) c->sss->lights |= 1u << light;
         V3 wi;
         float light_pdf_v;
         Ray shadow;
         Col L = light_sample(s, light, p_sample, 1e-5f, bs.ls_comp, bs.ls_geo[0], bs.ls_geo[1], &wi, &light_pdf_v, &shadow);
-        if (L == BLACK || light_pdf_v == 0.0f) continue;
+        if (L == BLACK || light_pdf_v == 0.0f) {
+            sss_note(c, SSS_SINGLE_BLACK);
+            continue;
+        }
         float maxt = shadow.maxt;
         Hit wh;
         wh.frag.n = V3(0, 0, 0);
@@ -2659,8 +2688,11 @@ Col l_bssrdf_single(LiCtx* c, const Frag& frag, uint32_t material, V3 wo, const 
                 V3 pwi = fwi.p, ni = fwi.n;
                 shadow.mint = shadow.maxt + wh.epsilon;
                 shadow.maxt = maxt;
-                if (!scene_occluded(s, shadow, &c->cnt)) {
+                const bool blocked = scene_occluded(s, shadow, &c->cnt);
+                sss_note(c, blocked ? SSS_SINGLE_OCCLUDED : SSS_SINGLE_ACCEPTED);
+                if (!blocked) {
                     const gbl_material mi = resolve_material(s, s->materials[material], fwi);
+                    if (memcmp(mi.color, mo.color, sizeof(mo.color)) != 0 || memcmp(mi.color2, mo.color2, sizeof(mo.color2)) != 0) sss_note(c, SSS_MI_DIFFERS);
                     float ph = phase_hg(wi, wo_refract, mo.k);
                     float cosi = absdot(ni, wi);
                     float Fti = 1.0f - fresnel_dielectric(cosi, 1.0f, eta);
@@ -2673,7 +2705,11 @@ Col l_bssrdf_single(LiCtx* c, const Frag& frag, uint32_t material, V3 wo, const 
                     Ls += (Ft * Fti * ph * scatter / sigma_tc) * exp_color(-di_prime * sigma_ti) * exp_color(-d * sigma_t) * L /
                           (light_pdf_v * pick_pdf * sample_pdf);
                 }
+            } else {
+                sss_note(c, SSS_SINGLE_OTHER);
             }
+        } else {
+            sss_note(c, SSS_SINGLE_MISS);
         }
     }
     Ls = Ls / static_cast<float>(c->ix->sss_n);
@@ -2698,6 +2734,7 @@ Col l_bssrdf_diffusion(LiCtx* c, const Frag& frag, uint32_t material, V3 wo, con
         Ray probe;
         float disc_pdf;
         int axis = bssrdf_sample_probe_ray(frag, bs.pick_axis, bs.disc[0], bs.disc[1], sigma_tr, rmax, &probe, &disc_pdf);
+        sss_note(c, axis == SSS_N_AXIS ? SSS_AXIS_N : axis == SSS_U_AXIS ? SSS_AXIS_U : SSS_AXIS_V);
         Hit ph;
         ph.frag.n = V3(0, 0, 0);
         ph.frag.dpdv = V3(0, 0, 0);
@@ -2706,6 +2743,7 @@ Col l_bssrdf_diffusion(LiCtx* c, const Frag& frag, uint32_t material, V3 wo, con
                 const Frag& pf = ph.frag;
                 V3 p_probe = pf.p;
                 const gbl_material mp = resolve_material(s, s->materials[material], pf);
+                if (memcmp(mp.color, mo.color, sizeof(mo.color)) != 0 || memcmp(mp.color2, mo.color2, sizeof(mo.color2)) != 0) sss_note(c, SSS_MP_DIFFERS);
                 Col Rd = bssrdf_rd(mp, A, sqlen(p_probe - pwo));
                 float pick_pdf;
                 int light = s->light_power.sample_discrete(bs.pick_light, &pick_pdf);
@@ -2714,14 +2752,26 @@ Col l_bssrdf_diffusion(LiCtx* c, const Frag& frag, uint32_t material, V3 wo, con
                 Ray shadow;
                 V3 ni = pf.n;
                 Col L = light_sample(s, light, p_probe, ph.epsilon, bs.ls_comp, bs.ls_geo[0], bs.ls_geo[1], &wi, &light_pdf_v, &shadow);
-                if (L == BLACK || light_pdf_v == 0.0f || scene_occluded(s, shadow, &c->cnt)) continue;
+                if (L == BLACK || light_pdf_v == 0.0f) {
+                    sss_note(c, SSS_PROBE_BLACK);
+                    continue;
+                }
+                if (scene_occluded(s, shadow, &c->cnt)) {
+                    sss_note(c, SSS_PROBE_OCCLUDED);
+                    continue;
+                }
+                sss_note(c, SSS_PROBE_ACCEPTED);
                 float cosi = absdot(ni, wi);
                 Col irradiance = L * cosi / (light_pdf_v * pick_pdf);
                 float Fti = 1.0f - fresnel_dielectric(cosi, 1.0f, eta);
                 float pdf = disc_pdf * absdot(probe.d, ni);
                 float w = bssrdf_mis_weight(frag, pf, axis, pdf, sigma_tr, rmax);
                 Lm += (w * INV_PI * Ft * Fti * Rd * irradiance) / pdf;
+            } else {
+                sss_note(c, SSS_PROBE_OTHER);
             }
+        } else {
+            sss_note(c, SSS_PROBE_MISS);
         }
     }
     Lm = Lm / static_cast<float>(c->ix->sss_n);
@@ -2735,6 +2785,19 @@ Col l_subsurface(LiCtx* c, const Hit& hit, V3 wo, const float* rec) {
     if (s->materials[material].type != GBL_MAT_SUBSURFACE || s->lights.empty()) return Col(0.0f);
     Col single = l_bssrdf_single(c, hit.frag, material, wo, rec);
     Col multi = l_bssrdf_diffusion(c, hit.frag, material, wo, rec);
+    if (c->sss) {
+        float* w = c->sss->w;
+        if (w[SSS_CALLS] == 0.0f) {
+            w[SSS_SINGLE] = single.r; w[SSS_SINGLE + 1] = single.g; w[SSS_SINGLE + 2] = single.b;
+            w[SSS_MULTI] = multi.r; w[SSS_MULTI + 1] = multi.g; w[SSS_MULTI + 2] = multi.b;
+            w[SSS_FIRST_LEVEL] = static_cast<float>(c->sss_level);
+        }
+        w[SSS_CALLS] += 1.0f;
+        w[SSS_MAX_LEVEL] = std::max(w[SSS_MAX_LEVEL], static_cast<float>(c->sss_level));
+        if (c->sss_level > 0) w[SSS_CALLS_DEEP] += 1.0f;
+        if (std::isnan(single.r) || std::isnan(single.g) || std::isnan(single.b)) c->sss->nan |= 1u;
+        if (std::isnan(multi.r) || std::isnan(multi.g) || std::isnan(multi.b)) c->sss->nan |= 2u;
+    }
     return single + multi;
 }
 
@@ -3020,6 +3083,7 @@ Col whitted_li(LiCtx* c, const Ray& ray_in, const float* rec, const RayDiff* dif
     // Lsubsurface with the fragment's differentials in place (GoblinWhitted.cpp:22-27: after computeUVDifferential, at every
     // level of the recursion, always from the camera sample's one BSSRDF block).  The material's Fresnel mirror lobe never
     // answers the two specular requests below: its type is BSDFAll
+    c->sss_level = depth;
     Li += l_subsurface(c, hit, -ray.d, rec);
     const ResolvedMat mat = resolve_hit_material(s, s->instances[hit.instance].material, hit.frag);
     Li += multi_sample_ld(c, ray, hit.epsilon, hit, mat, rec);
@@ -3559,6 +3623,16 @@ void orc_pt_offsets(const gbl_render_setting* rs, int32_t* out) {
     }
 }
 
+// Where a Sample record keeps its BSSRDF block: the offsets of {light component 1D, light geometry 2D, light pick 1D, axis pick
+// 1D, disc 2D, single-scatter distance 1D} and the number of slots (slot i reads offset + i, or offset + 2 i for a 2D pattern)
+void orc_sss_offsets(const orc_scene* s, const gbl_render_setting* rs, int32_t* out) {
+    PtIndices ix;
+    Quota q = make_quota(*rs, &ix, s);
+    out[0] = q.off1[ix.sss_ls1]; out[1] = q.off2[ix.sss_ls2]; out[2] = q.off1[ix.sss_pick];
+    out[3] = q.off1[ix.sss_axis]; out[4] = q.off2[ix.sss_disc]; out[5] = q.off1[ix.sss_single];
+    out[6] = static_cast<int32_t>(ix.sss_n);
+}
+
 // First `n` values of glibc rand() after srand(1)
 void orc_glibc_rand(int32_t* out, int32_t n) {
     GlibcRand g(1);
@@ -3690,6 +3764,30 @@ int32_t orc_medium(const orc_scene* s, const gbl_render_setting* rs, const float
     for (int64_t i = 0; i < n; ++i) {
         Col L = eval_li(&c, samples + i * dims);
         task_sample(&c, samples + i * dims, L, out + 8 * i);
+    }
+    return 0;
+}
+
+// The subsurface probe: per record SSS_PROBE_WORDS floats (the SSS_* words above) noted by the very l_subsurface that
+// orc_li_replay and orc_render evaluate, under the record's own draws; li_out (optional) receives what orc_li_replay gives.
+int32_t orc_subsurface(const orc_scene* s, const gbl_render_setting* rs, const float* samples, int64_t n, float* out, float* li_out) {
+    if (!s || !rs || !samples || !out) return -1;
+    PtIndices ix;
+    Quota q = make_quota(*rs, &ix, s);
+    const uint32_t dims = q.dims();
+    LiCtx c;
+    c.s = s; c.rs = rs; c.q = &q; c.ix = &ix; c.rng = nullptr; c.ref_faithful = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        SssProbe probe;
+        c.sss = &probe;
+        c.sss_level = 0;
+        Col L = eval_li(&c, samples + i * dims);
+        c.sss = nullptr;
+        if (s->volume.on) L = task_sample(&c, samples + i * dims, L);
+        probe.w[SSS_LIGHTS] = static_cast<float>(probe.lights);
+        probe.w[SSS_NAN] = static_cast<float>(probe.nan);
+        memcpy(out + SSS_PROBE_WORDS * i, probe.w, sizeof(probe.w));
+        if (li_out) { li_out[4 * i] = L.r; li_out[4 * i + 1] = L.g; li_out[4 * i + 2] = L.b; li_out[4 * i + 3] = L.a; }
     }
     return 0;
 }

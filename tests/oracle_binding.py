@@ -76,6 +76,10 @@ def lib():
         L.orc_render_medium.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
         L.orc_render_medium.restype = C.c_int32
+        L.orc_subsurface.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.orc_subsurface.restype = C.c_int32
+        L.orc_sss_offsets.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.POINTER(C.c_int32)]
+        L.orc_sss_offsets.restype = None
         L.orc_hardware_threads.restype = C.c_int32
         L.orc_mip_lookup.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
         L.orc_mip_lookup.restype = C.c_int32
@@ -199,6 +203,34 @@ class Oracle:
         if lib().orc_render_medium(self.h, C.byref(s), sampler, seed, _ptr(film), _ptr(samples), _ptr(li), _ptr(medium)) != 0:
             raise RuntimeError("orc_render_medium failed (no medium in the scene?)")
         return {"film": film, "samples": samples, "li": li, "medium": medium}
+
+    # the subsurface probe's words (columns of a record)
+    SSS_SINGLE, SSS_MULTI, SSS_CALLS, SSS_CALLS_DEEP = slice(0, 3), slice(3, 6), 6, 7
+    SSS_AXIS_N, SSS_AXIS_U, SSS_AXIS_V, SSS_PROBE_MISS, SSS_PROBE_OTHER, SSS_PROBE_BLACK, SSS_PROBE_OCCLUDED, SSS_PROBE_ACCEPTED = range(8, 16)
+    SSS_SINGLE_BLACK, SSS_SINGLE_MISS, SSS_SINGLE_OTHER, SSS_SINGLE_OCCLUDED, SSS_SINGLE_ACCEPTED, SSS_LIGHTS, SSS_NAN, SSS_FIRST_LEVEL = range(16, 24)
+    SSS_MI_DIFFERS, SSS_MP_DIFFERS, SSS_MAX_LEVEL, SSS_WORDS = 24, 25, 26, 28
+
+    def sss_offsets(self, setting=None):
+        """Where a Sample record keeps its BSSRDF block: dict of the columns of slot 0's {ls_comp, ls_geo, pick_light, pick_axis,
+        disc, single} (slot i: + i, or + 2 i for the two 2D patterns ls_geo and disc) and `n`, the number of slots."""
+        out = (C.c_int32 * 7)()
+        lib().orc_sss_offsets(self.h, C.byref(setting or self.scene.desc.setting), out)
+        return dict(zip(("ls_comp", "ls_geo", "pick_light", "pick_axis", "disc", "single", "n"), (int(v) for v in out)))
+
+    def subsurface(self, samples, setting=None):
+        """What Lsubsurface did in li_replay, per record (n, 28): {single rgb, multi rgb} of the sample's first evaluation, the number
+        of evaluations (and of those at a recursion level > 0), and counters over their slots -- probe axis N / U / V; probe ray
+        missed / hit another material / hit the same one with a black light sample, an occluded one, an accepted one; single
+        scatter's light sample black, its exit missed / on another material / occluded / accepted; a bit mask of the lights picked;
+        1 | 2 for a NaN single | multi term; the first evaluation's level; slots whose single-scatter exit / probe fragment resolved
+        other coefficients than the shaded fragment; the deepest evaluation's level.  Returns (records, li) with li what li_replay gives."""
+        s = setting or self.scene.desc.setting
+        samples = np.ascontiguousarray(samples, np.float32)
+        assert samples.shape[1] == self.dims(s), (samples.shape, self.dims(s))
+        out, li = np.zeros((samples.shape[0], self.SSS_WORDS), np.float32), np.zeros((samples.shape[0], 4), np.float32)
+        if lib().orc_subsurface(self.h, C.byref(s), _ptr(samples), samples.shape[0], _ptr(out), _ptr(li)) != 0:
+            raise RuntimeError("orc_subsurface failed")
+        return out, li
 
     def splat(self, samples, li, film=None):
         d = self.scene.desc
