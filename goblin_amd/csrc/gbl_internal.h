@@ -66,6 +66,8 @@ struct gbl_ctx {
     gbl_buf temporal;         // gbl_film_accumulate's prepared frame (kernels/temporal.h): cl, nz (float4 each) and the flags
     gbl_buf motion;           // gbl_render_motion's previous-transform table and moved flags (kernels/motion_args.h) ...
     std::vector<unsigned char> h_motion;   // ... and the host copy they are uploaded from
+    gbl_buf motion_deform;    // gbl_render_motion_deform's per-mesh table, then the deformed meshes' previous positions (motion_stage.h) ...
+    std::vector<unsigned char> h_motion_deform;   // ... and the host copy they are uploaded from
     std::map<int, float> auto_rays_per_path;   // GBL_SCHEDULE_AUTO's pilot: rays per camera path by 2 * max_ray_depth + russian_roulette (gbl_render)
     double build_ms = 0.0;    // pack_scene + BVH construction + node / triangle upload
     // what gbl_update_camera and gbl_film_accumulate need to pack a camera (scene_prep.h pack_camera)
@@ -174,8 +176,9 @@ void gbl_launch_temporal_prepare(const float* film, const float* variance, const
 void gbl_launch_temporal_accumulate(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance, const float* history_in,
                                     float* history_out, float* film_out, float* variance_out, const TemporalArgs& a, hipStream_t stream);
 // kernels_motion.hip: gbl_render_motion's kernels (kernels/motion.h) -- the packet kernel, or one ray per lane, lean or EXT -- and
-// gbl_film_accumulate_motion's accumulate pass (kernels/temporal.h with the reprojection read from the motion planes)
-gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext);
+// gbl_film_accumulate_motion's accumulate pass (kernels/temporal.h with the reprojection read from the motion planes).
+// deform: the flavours of gbl_render_motion_deform that follow a deformed mesh's hit through its previous pose
+gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext, bool deform = false);
 void gbl_launch_temporal_accumulate_motion(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance,
                                            const float* history_in, float* history_out, float* film_out, float* variance_out, const float* motion,
                                            const TemporalArgs& a, hipStream_t stream);

@@ -9,6 +9,8 @@
 //                          whose answer depends on the visiting order traced again on its own, as aov_packet_kernel<false> does
 //   motion_kernel<EXT>     one ray per lane with the LDS stack: the EXT scenes (shapes, masks, thin-lens or orthographic context
 //                          camera) and, EXT = false, lean scenes whose tree is too deep for the packet's stack
+//   motion_packet_deform_kernel, motion_deform_kernel<EXT>   the same three for gbl_render_motion_deform when some mesh is
+//                          deformed (mo_write<true>): a hit of such a mesh is followed through the triangle's previous pose
 // Planes (W * H float4 each): M0 = {image_x, image_y, z_exp, ok}, all zero unless ok; M1 = {n_b.xyz, instance + 1 or 0}.
 // Plain IEEE single arithmetic in the order written (-ffp-contract=off), the projection being temporal.h's tp_project itself.
 #pragma once
@@ -16,7 +18,45 @@
 #include "packet.h"
 #include "temporal.h"
 
-// Pixel (x, y) of the image, which the caller has checked to lie inside it: the two texels of the pixel.
+// gbl_render_motion_deform's hit of instance `ip` of a deformed triangle mesh (`off`: the mesh's entry of MotionArgs::mesh_prev):
+// the hit's barycentrics on the triangle's previous pose, taken to the previous frame's world by `m` -- the instance's previous
+// toWorld rows if it moved, else its current ones -- and, with a normal film, the normal carried by the inverse transpose of the
+// triangle's own deformation between `u = xf_normal(ip->m, nn)` and `inv`, the inverse rows that go with `m`.  False, and nothing
+// written, for a vertex outside the packed positions (the host's tables never hold one).
+__device__ __forceinline__ bool mo_deformed(const DevScene& sc, const MotionArgs& a, const Hit& hit, const DevInstance* ip, int32_t off, const float* m,
+                                            const float* inv, F3 nn, F3* P, F3* nb) {
+    const DevTri* T = sc.tris + hit.tri;
+    const DevTriShade s = sc.tri_shade[T->shade];
+    F3 v[3];
+    for (int k = 0; k < 3; ++k) {
+        const int64_t at = static_cast<int64_t>(s.v[k]) + off;
+        if (at < 0 || at >= static_cast<int64_t>(a.prev_count)) return false;
+        const float* p = a.prev_pos + 3 * static_cast<size_t>(at);
+        v[k] = f3(p[0], p[1], p[2]);
+    }
+    const F3 e1p = v[1] - v[0], e2p = v[2] - v[0];
+    *P = xf_point(m, (v[0] + e1p * hit.b1) + e2p * hit.b2);
+    if (a.normal) {
+        const F3 u = xf_normal(ip->m, nn);
+        const F3 e1 = f3(T->e1[0], T->e1[1], T->e1[2]), e2 = f3(T->e2[0], T->e2[1], T->e2[2]);
+        const F3 g = cross(e1, e2), gp = cross(e1p, e2p);
+        const float L = sqrtf((g.x * g.x + g.y * g.y) + g.z * g.z), Lp = sqrtf((gp.x * gp.x + gp.y * gp.y) + gp.z * gp.z);
+        F3 xx = u;   // a triangle without area in either pose: the instance alone carries the normal
+        if (L > 0.0f && Lp > 0.0f) {
+            const F3 gh = f3(g.x / L, g.y / L, g.z / L), ghp = f3(gp.x / Lp, gp.y / Lp, gp.z / Lp);
+            const float c1 = dot(e1, u), c2 = dot(e2, u), c3 = dot(gh, u);
+            xx = (cross(e2p, ghp) * (c1 / Lp) + cross(ghp, e1p) * (c2 / Lp)) + ghp * c3;   // e1'.x = c1, e2'.x = c2, g^'.x = c3
+        }
+        const F3 w = xf_normal(inv, xx);
+        const float len = sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z);
+        *nb = len > 0.0f ? f3(w.x / len, w.y / len, w.z / len) : f3(0.0f, 0.0f, 0.0f);
+    }
+    return true;
+}
+
+// Pixel (x, y) of the image, which the caller has checked to lie inside it: the two texels of the pixel.  DEFORM: a hit of a
+// triangle mesh whose previous pose the call was given goes through mo_deformed; every other hit takes the path below it.
+template <bool DEFORM>
 __device__ __forceinline__ void mo_write(const DevScene& sc, const MotionArgs& a, int x, int y, bool got, const Hit& hit, F3 o, F3 d) {
     const int n = a.W * a.H, pi = y * a.W + x;
     F3 nn = f3(0.0f, 0.0f, 0.0f);
@@ -35,7 +75,22 @@ __device__ __forceinline__ void mo_write(const DevScene& sc, const MotionArgs& a
     if (got) {
         const int i = hit.inst;
         F3 P = o + d * hit.t;
-        if (a.moved != nullptr && a.moved[i] != 0u) {
+        bool deformed = false;
+        if constexpr (DEFORM) {
+            const DevInstance* ip = sc.instances + i;
+            const uint32_t mesh = static_cast<uint32_t>(ip->mesh);
+            const int32_t off = ip->shape == 0u && mesh < a.num_meshes ? a.mesh_prev[mesh] : GBL_MOTION_STATIC;
+            if (off != GBL_MOTION_STATIC) {
+                const float* m = ip->m;
+                const float* inv = ip->inv;
+                if (a.moved != nullptr && a.moved[i] != 0u) {
+                    m = a.prev_xf + static_cast<size_t>(GBL_MOTION_XF_FLOATS) * static_cast<size_t>(i);
+                    inv = m + 12;
+                }
+                deformed = mo_deformed(sc, a, hit, ip, off, m, inv, nn, &P, &nb);
+            }
+        }
+        if (!deformed && a.moved != nullptr && a.moved[i] != 0u) {
             const DevInstance* ip = sc.instances + i;
             const float* pm = a.prev_xf + static_cast<size_t>(GBL_MOTION_XF_FLOATS) * static_cast<size_t>(i);
             P = xf_point(pm, xf_point(ip->inv, P));
@@ -67,7 +122,8 @@ __device__ __forceinline__ bool mo_pixel(const MotionArgs& a, int* x, int* y) {
 __device__ __forceinline__ float mo_mint(const DevCamera& c) { return c.type == 1u ? 0.0f : 1e-3f; }   // render_kernels.h camera_ray
 
 // LDS: the waves' shared stacks (static) and the lanes' own for the retraces (dynamic, stack_lds_bytes), as aov_packet_kernel
-__global__ __launch_bounds__(GBL_BLOCK) void motion_packet_kernel(DevScene sc, MotionArgs a) {
+template <bool DEFORM>
+__device__ __forceinline__ void motion_packet(const DevScene& sc, const MotionArgs& a) {
     __shared__ uint32_t pk_stack[(GBL_BLOCK / 64) * GBL_PACKET_STACK_WORDS];
     extern __shared__ __align__(16) unsigned char smem[];
     gbl_lds_u32* const wstack = gbl_as_lds(pk_stack + (threadIdx.x >> 6) * GBL_PACKET_STACK_WORDS);
@@ -85,11 +141,11 @@ __global__ __launch_bounds__(GBL_BLOCK) void motion_packet_kernel(DevScene sc, M
         LaneCounters scratch = {};
         got = trace<false, false, false, false>(sc, o, d, mint, INFINITY, stk, hit, scratch);
     }
-    if (live) mo_write(sc, a, x, y, got, hit, o, d);
+    if (live) mo_write<DEFORM>(sc, a, x, y, got, hit, o, d);
 }
 
-template <bool EXT>
-__global__ __launch_bounds__(GBL_BLOCK, EXT ? 2 : 4) void motion_kernel(DevScene sc, MotionArgs a) {
+template <bool EXT, bool DEFORM>
+__device__ __forceinline__ void motion_lane(const DevScene& sc, const MotionArgs& a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const LdsStack stk = {gbl_as_lds(reinterpret_cast<uint32_t*>(smem) + threadIdx.x)};
     int x, y;
@@ -100,5 +156,11 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? 2 : 4) void motion_kernel(DevScene
     Hit hit;
     LaneCounters cnt = {};
     const bool got = trace<false, false, EXT, false>(sc, o, d, mo_mint(sc.camera), INFINITY, stk, hit, cnt);
-    mo_write(sc, a, x, y, got, hit, o, d);
+    mo_write<DEFORM>(sc, a, x, y, got, hit, o, d);
 }
+template <bool EXT>
+__global__ __launch_bounds__(GBL_BLOCK, EXT ? 2 : 4) void motion_kernel(DevScene sc, MotionArgs a) { motion_lane<EXT, false>(sc, a); }
+template <bool EXT>
+__global__ __launch_bounds__(GBL_BLOCK, EXT ? 2 : 4) void motion_deform_kernel(DevScene sc, MotionArgs a) { motion_lane<EXT, true>(sc, a); }
+__global__ __launch_bounds__(GBL_BLOCK) void motion_packet_kernel(DevScene sc, MotionArgs a) { motion_packet<false>(sc, a); }
+__global__ __launch_bounds__(GBL_BLOCK) void motion_packet_deform_kernel(DevScene sc, MotionArgs a) { motion_packet<true>(sc, a); }

@@ -4,7 +4,11 @@
 #define GBL_TEMPORAL_NO_PREPARE   // temporal_prepare_kernel is kernels_temporal.hip's
 #include "kernels/motion.h"
 
-gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext) {
+gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext, bool deform) {
+    if (deform) {
+        if (packet) return motion_packet_deform_kernel;
+        return ext ? motion_deform_kernel<true> : motion_deform_kernel<false>;
+    }
     if (packet) return motion_packet_kernel;
     return ext ? motion_kernel<true> : motion_kernel<false>;
 }

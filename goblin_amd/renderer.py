@@ -394,12 +394,15 @@ class HipPathTracer:
         torch = _torch()
         return torch.zeros((3, self.info.yres, self.info.xres, 4), dtype=torch.float32, device=self.device)
 
-    def motion(self, prev_camera, prev_instances=None, normal=None):
+    def motion(self, prev_camera, prev_instances=None, normal=None, prev_vertices=None):
         """Motion planes of the current frame (gbl_render_motion) on the current stream: a (2, yres, xres, 4) float32 tensor --
         [0] = {image_x, image_y, z_exp, ok}, where the surface under each pixel's centre lay under ``prev_camera`` (a gbl_camera)
         and, for an instance that moved since, under its transform in ``prev_instances`` (``instances()`` as it was when the
         previous frame was rendered; None: no instance moved); [1] = {the current normal carried into the previous frame, instance
-        + 1 or 0}, the normal taken from ``normal`` (render_aov's film; zeros without one).  ``accumulate(motion=...)`` reads it."""
+        + 1 or 0}, the normal taken from ``normal`` (render_aov's film; zeros without one).  ``accumulate(motion=...)`` reads it.
+        ``prev_vertices``: {mesh: (vertex_count, 3) float32 array}, ``vertices(mesh)`` as it was when the previous frame was
+        rendered, for every mesh ``update_vertices`` edited since (gbl_render_motion_deform): a surface that deformed is followed
+        through its triangle's previous pose.  A mesh whose positions are the context's own counts as not deformed."""
         torch = _torch()
         h, w = self.info.yres, self.info.xres
         p = _abi.gbl_motion_params()
@@ -421,7 +424,24 @@ class HipPathTracer:
             p.normal_accum = normal.data_ptr()
         p.stream = torch.cuda.current_stream(self.device).cuda_stream
         out = torch.empty((2, h, w, 4), dtype=torch.float32, device=self.device)
-        st = self.lib.gbl_render_motion(self.handle, C.byref(p), out.data_ptr())
+        if prev_vertices is None:
+            st = self.lib.gbl_render_motion(self.handle, C.byref(p), out.data_ptr())
+        else:
+            keep = []       # the arrays the list points into, alive across the call
+            listed = (_abi.gbl_motion_mesh * max(len(prev_vertices), 1))()
+            for k, (mesh, positions) in enumerate(prev_vertices.items()):
+                mesh = int(mesh)
+                pos = np.ascontiguousarray(positions, np.float32)
+                if 0 <= mesh < self.scene.desc.num_meshes and self.scene.desc.meshes[mesh].shape == 0:
+                    count = int(self.scene.desc.meshes[mesh].vertex_count)
+                    if pos.shape != (count, 3):
+                        raise ValueError("prev_vertices[%d] must have shape (%d, 3), got %s" % (mesh, count, pos.shape))
+                elif mesh < 0:
+                    raise ValueError("prev_vertices: mesh %d is out of range" % mesh)
+                keep.append(pos)
+                listed[k].mesh, listed[k].reserved, listed[k].positions = mesh, 0, pos.ctypes.data
+            st = self.lib.gbl_render_motion_deform(self.handle, C.byref(p), listed, len(prev_vertices), out.data_ptr())
+            del keep
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return out

@@ -643,6 +643,31 @@ typedef struct gbl_motion_params {
 } gbl_motion_params;
 gbl_status gbl_render_motion(gbl_ctx* ctx, const gbl_motion_params* params, float* motion_out);
 
+/* gbl_render_motion for meshes whose vertices were edited since the previous frame (gbl_update_vertices): the same ray, query,
+ * miss handling, planes and refusals, and the previous pose of every mesh in prev_meshes.  A listed mesh is DEFORMED iff its
+ * previous positions differ bitwise from the ones the context holds (gbl_get_vertices); a listed but unchanged mesh, an unlisted
+ * one, a sphere and a disk take gbl_render_motion's path, so with num_prev_meshes == 0 or every listed mesh unchanged the planes
+ * are gbl_render_motion's bit for bit.  On a hit of instance i of a deformed mesh, in triangle T at barycentrics (b1, b2):
+ *   Q = (v0' + (v1' - v0') b1) + (v2' - v0') b2      T's vertices in the previous pose, object space
+ *   P_prev = M Q                                      M: the instance's previous transform if it moved, else its current one
+ * projected as gbl_render_motion projects its point; M1.w = i + 1 as there.  With a normal film, n_b is the film's normal carried
+ * by the inverse transpose of the map that takes T's current edges and unit normal to the previous ones (to object space by the
+ * instance's current transform first, on to the previous frame's world by M afterwards), unit length or 0; a triangle without
+ * area in either pose carries it by the instance's transforms alone.
+ * Limits: only the first hit is followed -- shadows, reflections and refractions of a deforming surface are not tracked; a map
+ * that perturbs the shading normal is carried as the film's normal by the geometric deformation.
+ * GBL_ERR_INVALID, before the context is touched: everything gbl_render_motion refuses, a NULL prev_meshes with
+ * num_prev_meshes > 0, a NULL positions, a mesh index out of range or a mesh that is a sphere or a disk, a mesh listed twice,
+ * reserved != 0 and a non-finite coordinate.  The previous positions of the deformed meshes are copied to a table of the context
+ * and uploaded on params->stream, as the previous transforms are; the caller's arrays are not read after the call returns. */
+typedef struct gbl_motion_mesh {
+    uint32_t mesh;            /* gbl_scene_desc::meshes index of a triangle mesh */
+    uint32_t reserved;        /* 0 */
+    const float* positions;   /* host, 3 * vertex_count: gbl_get_vertices(mesh) as it was when the previous frame was rendered */
+} gbl_motion_mesh;
+gbl_status gbl_render_motion_deform(gbl_ctx* ctx, const gbl_motion_params* params, const gbl_motion_mesh* prev_meshes,
+                                    uint32_t num_prev_meshes, float* motion_out);
+
 /* gbl_film_accumulate with the reprojection read from `motion` (gbl_render_motion's planes for this frame) instead of
  * computed from the depth film and params->prev_camera, which is not read: (image_x, image_y, z_exp) = M0.xyz, a pixel with
  * M0.w == 0 has no history, and with a normal film the taps are tested against M1.xyz in place of n (H2 still stores n).
@@ -704,7 +729,8 @@ gbl_status gbl_get_instances(const gbl_ctx* ctx, uint32_t first, uint32_t count,
  *    but slower to trace than a new one: re-create the context to rebuild it.
  *  - The call synchronises the device, as gbl_update_instances does, and GBL_SCHEDULE_AUTO measures its rays per path again.
  *  - normals == NULL: the mesh's vertex normals stay as they were.  The caller owns that choice.
- *  - gbl_render_motion goes on treating vertices as static: its planes follow cameras and instances only.
+ *  - gbl_render_motion's planes follow cameras and instances only; gbl_render_motion_deform also takes the positions a mesh had
+ *    in the previous frame (gbl_get_vertices before the edit) and follows the deformation of the surface under each pixel.
  * GBL_ERR_INVALID, the context untouched: a NULL ctx or positions, a mesh index out of range or a mesh that is a sphere or a
  * disk, a vertex range out of bounds, a non-finite coordinate, normals given for a mesh without has_normal.
  * GBL_ERR_UNSUPPORTED, the context untouched: a mesh an area light emits from (its emitting triangles, area distribution and

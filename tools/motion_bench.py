@@ -5,6 +5,11 @@ same frame and a 1-spp gbl_render_aov of the same context, in the same process, 
 the Cornell box at 1024^2.  tools/temporal_bench.py's method: HIP events, one warm-up round, the median and the spread of --calls
 rounds, each timing --batch calls between two events, divided.  Prints one JSON line.
 
+On the bunny also gbl_render_motion_deform (DESIGN.md 4.8 "Deforming meshes"): the bunny twisted by 10 degrees (tools/refit_bench.py's
+twist) with its untwisted positions as the previous pose -- no mesh deformed (the current positions listed), deformed with a normal
+film, deformed without one -- beside gbl_render_motion of the same context; and "deform_upload_ms", the host-to-device copy of the
+previous positions and the per-mesh table alone, on the same stream.
+
     python tools/motion_bench.py [--calls 7] [--batch 10] [--configs bunny cornell]
 """
 import argparse
@@ -14,11 +19,13 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from goblin_amd import _abi  # noqa: E402
 from goblin_amd import scene as gs  # noqa: E402
 from goblin_amd.renderer import HipPathTracer  # noqa: E402
+from refit_bench import twisted  # noqa: E402
 from temporal_bench import CONFIGS, summary, timed  # noqa: E402
 
 
@@ -70,6 +77,31 @@ def main():
         row["motion_over_aov_1spp"] = med["motion_static"] / med["aov_1spp"]
         row["accumulate_motion_over_accumulate"] = {"variance_plane": med["accumulate_motion_variance_plane"] / med["accumulate_variance_plane"],
                                                     "spatial": med["accumulate_motion_spatial"] / med["accumulate_spatial"]}
+        if name == "bunny":
+            rest = r.vertices(0)
+            r.update_vertices(0, twisted(rest, 10.0))
+            now = r.vertices(0)
+            nbytes = rest.nbytes + 4 * int(r.scene.desc.num_meshes)
+            host = np.zeros(nbytes, np.uint8)        # pageable, as the context's staging copy is
+            dev = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+            deform = {
+                "deform_motion_static": lambda: timed(lambda: r.motion(prev, None, normal=films["normal"]), a.batch),
+                "deform_none_deformed": lambda: timed(lambda: r.motion(prev, None, normal=films["normal"], prev_vertices={0: now}), a.batch),
+                "deform_deformed": lambda: timed(lambda: r.motion(prev, None, normal=films["normal"], prev_vertices={0: rest}), a.batch),
+                "deform_deformed_no_normal": lambda: timed(lambda: r.motion(prev, None, prev_vertices={0: rest}), a.batch),
+                "deform_upload": lambda: timed(lambda: dev.copy_(torch.from_numpy(host), non_blocking=True), a.batch),
+            }
+            dtimes = {k: [] for k in deform}
+            for rep in range(a.calls + 1):
+                for k, fn in deform.items():
+                    ms = fn()
+                    if rep:
+                        dtimes[k].append(ms)
+            row.update({k: summary(v) for k, v in dtimes.items()})
+            med = {k: row[k]["median_ms"] for k in deform}
+            row["deform_over_motion"] = {k: med[k] / med["deform_motion_static"] for k in ("deform_none_deformed", "deform_deformed", "deform_deformed_no_normal")}
+            row["deform_vertices"] = int(len(rest))
+            row["deform_upload_bytes"] = int(nbytes)
         row["pixels"] = res[0] * res[1]
         row["instances"] = len(still)
         row["pixels_with_history"] = float((r.accumulate(beauty, films["depth"], variance, films["normal"], history, motion=planes)["history"][0, ..., 3] > 1).float().mean())
