@@ -13,6 +13,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 GBL_ABI_VERSION = 14
 GBL_AUTO_WAVEFRONT_RAYS_PER_PATH, GBL_AUTO_WAVEFRONT_PATHS = 6.0, 1 << 22   # gbl_schedule AUTO thresholds (goblin_hip.h)
 GBL_OK, GBL_ERR_INVALID, GBL_ERR_UNSUPPORTED, GBL_ERR_IO, GBL_ERR_DEVICE, GBL_ERR_OOM, GBL_ERR_INTERNAL = range(7)
+GBL_VERTICES_DEFER_ORDER = 1   # gbl_update_vertices_device flags
 STATUS_NAMES = {0: "GBL_OK", 1: "GBL_ERR_INVALID", 2: "GBL_ERR_UNSUPPORTED", 3: "GBL_ERR_IO",
                 4: "GBL_ERR_DEVICE", 5: "GBL_ERR_OOM", 6: "GBL_ERR_INTERNAL"}
 
@@ -195,7 +196,7 @@ HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "
                 "gbl_host_bloom", "gbl_host_tone_map", "gbl_host_write_ppm", "gbl_host_write_ppm8", "gbl_host_write_exr", "gbl_host_write_image",
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_selftest_geometry", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
                "gbl_aov_resolve_depth", "gbl_film_variance", "gbl_film_denoise", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
@@ -294,6 +295,10 @@ def hip_lib():
         lib.gbl_get_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(gbl_trs)]
         lib.gbl_update_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.gbl_get_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.gbl_update_vertices_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.gbl_get_vertices_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.gbl_order_pending.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.gbl_render_motion_deform_device.argtypes = [C.c_void_p, C.POINTER(gbl_motion_params), C.POINTER(gbl_motion_mesh), C.c_uint32, C.c_void_p]
         lib.gbl_selftest_geometry.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
         lib.gbl_update_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
         lib.gbl_get_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]

@@ -76,6 +76,8 @@ gbl_status gbl_render_aov_impl(gbl_ctx* ctx, const gbl_render_params* p, const g
     const bool ext = sc.extended != 0 || pl.replay || pl.want_stats;
     const bool packet = !ext && knobs.packet && sc.stack_entries <= 64;   // (kernels/packet.h GBL_PACKET_STACK, as primary_pass)
     gbl_aov_kernel kernel = packet ? gbl_kernel_aov_packet(p->exact_ties != 0) : gbl_kernel_aov(pl.replay, pl.want_stats, ext, p->exact_ties != 0);
+    // (every EXT build and both exact_ties builds read tri_order; the two lean ones leave a deferred vertex edit's tie order pending)
+    if ((st = make_orders_if(ctx, ext || p->exact_ties != 0)) != GBL_OK) return st;
     const size_t lds = stack_lds_bytes(sc);
     if ((st = allow_lds(ctx, kernel, lds + (packet ? 4096 : 0))) != GBL_OK) return st;   // (the packet kernel's static 3 KB count against the same limit)
     if (stats) HIP_TRY(ctx, hipEventRecord(ctx->ev0, stream));

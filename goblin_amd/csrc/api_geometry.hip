@@ -1,8 +1,11 @@
 // libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): vertex edits.  gbl_update_vertices refits a
 // mesh's BLAS on the device in place (kernels/refit.h over the plan of scene_refit.h); gbl_get_vertices and the
-// geometry tables' read-back go with it.
+// geometry tables' read-back go with it.  gbl_update_vertices_device and gbl_get_vertices_device are the same two over device
+// memory (kernels/vertices.h): the host copy of the positions turns into a mirror refreshed on demand, and the tie order may
+// wait for its first reader (make_pending_orders, gbl_host.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +17,36 @@
 #include "gbl_host.h"
 #include "scene_prep.h"
 #include "scene_refit.h"
+
+gbl_status refresh_mirror(gbl_ctx* ctx, uint32_t mesh) {
+    if (mesh >= ctx->mirror_stale.size() || !ctx->mirror_stale[mesh]) return GBL_OK;
+    const gbl_mesh& gm = ctx->h_meshes[mesh];
+    const size_t f0 = 3 * static_cast<size_t>(gm.vertex_offset), floats = 3 * static_cast<size_t>(gm.vertex_count);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (floats > 0) HIP_TRY(ctx, hipMemcpy(ctx->h_positions.data() + f0, ctx->scene.positions + f0, floats * sizeof(float), hipMemcpyDeviceToHost));
+    ctx->mirror_stale[mesh] = 0;
+    return GBL_OK;
+}
+
+gbl_status check_device_pointer(gbl_ctx* ctx, const void* p, uint64_t bytes, const std::string& who, const char* what) {
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) (void)hipGetLastError();   // (a plain host pointer: the runtime would hand the error to the next call that asks)
+    if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged) || attr.device != ctx->device)
+        return fail(ctx, GBL_ERR_INVALID, who + ": " + what + " is not device memory of device " + std::to_string(ctx->device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, GBL_ERR_INVALID, who + ": " + what + ": the allocation it points into is not known");
+    }
+    const uint64_t at = static_cast<uint64_t>(reinterpret_cast<uintptr_t>(p) - reinterpret_cast<uintptr_t>(base));
+    if (at > size || size - at < bytes)
+        return fail(ctx, GBL_ERR_INVALID, who + ": " + what + ": its allocation ends after " + std::to_string(size - std::min<uint64_t>(at, size)) + " bytes, " +
+                                              std::to_string(bytes) + " are read or written");
+    return GBL_OK;
+}
 
 namespace {
 
@@ -49,31 +82,74 @@ gbl_status ensure_plan(gbl_ctx* ctx, uint32_t mesh) {
     return GBL_OK;
 }
 
-gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, const float* positions, const float* normals) {
-    if (!ctx) return GBL_ERR_INVALID;
+// What both vertex edits refuse before they look at a coordinate, in gbl_update_vertices' order and words
+gbl_status check_edit_range(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, const float* positions) {
     if (!positions) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices: positions is NULL");
     if (mesh >= ctx->h_meshes.size()) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices: mesh " + std::to_string(mesh) + " is out of range");
     const gbl_mesh& gm = ctx->h_meshes[mesh];
     if (gm.shape != GBL_SHAPE_MESH) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices: mesh " + std::to_string(mesh) + " is a sphere or a disk: it has no vertices");
     if (static_cast<uint64_t>(first) + count > gm.vertex_count) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices: vertex range out of bounds");
-    for (size_t i = 0; i < 3 * static_cast<size_t>(count); ++i)
-        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i])))
-            return fail(ctx, GBL_ERR_INVALID, std::string("gbl_update_vertices: a ") + (std::isfinite(positions[i]) ? "normal" : "position") + " of vertex " +
-                                                  std::to_string(first + i / 3) + " is not finite");
-    if (normals && !gm.has_normal) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices: normals given for a mesh without vertex normals (has_normal)");
+    return GBL_OK;
+}
+
+// ... and after they have: float `i` of the edit is not finite, in its positions or else in its normals
+gbl_status fail_not_finite(gbl_ctx* ctx, uint32_t first, size_t i, bool position) {
+    return fail(ctx, GBL_ERR_INVALID, std::string("gbl_update_vertices: a ") + (position ? "position" : "normal") + " of vertex " + std::to_string(first + i / 3) + " is not finite");
+}
+
+gbl_status check_edit_allowed(gbl_ctx* ctx, uint32_t mesh, bool normals) {
+    if (normals && !ctx->h_meshes[mesh].has_normal) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices: normals given for a mesh without vertex normals (has_normal)");
     if (ctx->mesh_emits[mesh])
         return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_vertices: mesh " + std::to_string(mesh) + " is the geometry of an area light, whose emitting "
                                               "triangles, area distribution and power would have to follow; re-create the context instead");
     if (ctx->has_directional)
         return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_vertices: a directional or image based light's power (and the image based light's sampling sphere) "
                                               "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead");
+    return GBL_OK;
+}
+
+// The refit launches over the mesh's positions as the device holds them: triangles and their bounds, then the nodes from the
+// deepest level to the root (the stream orders the launches)
+void launch_refit(gbl_ctx* ctx, uint32_t mesh) {
+    const gbl_ctx::MeshRefit& mr = ctx->refit[mesh];
+    const DevScene& sc = ctx->scene;
+    gbl_launch_refit_tris(const_cast<DevTri*>(sc.tris), const_cast<DevTriBound*>(sc.tri_bounds), sc.tri_shade, sc.positions,
+                          static_cast<uint32_t>(ctx->h_positions.size() / 3), ctx->mesh_tri_first[mesh], ctx->h_meshes[mesh].tri_count, 0);
+    for (size_t l = mr.level_first.size(); l-- > 1;)
+        gbl_launch_refit_level(const_cast<DevNode*>(sc.nodes), sc.tri_bounds, mr.plan, mr.node_box, mr.level_first[l - 1], mr.level_first[l], 0);
+}
+
+// The reference's visiting order over the mesh's positions as the (fresh) mirror holds them -- what exact_ties, replay, stream
+// and the EXT builds break ties by -- into the mesh's slice of tri_order; the mesh is no longer pending
+gbl_status make_order(gbl_ctx* ctx, uint32_t mesh) {
+    const gbl_mesh& gm = ctx->h_meshes[mesh];
+    std::vector<DevTriOrder> order(gm.tri_count);
+    mesh_reference_order(ctx->h_positions.data() + 3 * static_cast<size_t>(gm.vertex_offset), ctx->h_indices.data() + 3 * static_cast<size_t>(gm.tri_offset), gm.tri_count,
+                         order.data());
+    if (!order.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevTriOrder*>(ctx->scene.tri_order) + gm.tri_offset, order.data(), order.size() * sizeof(DevTriOrder), hipMemcpyHostToDevice));
+    if (mesh < ctx->order_pending.size() && ctx->order_pending[mesh]) {
+        ctx->order_pending[mesh] = 0;
+        ctx->orders_pending -= 1;
+    }
+    return GBL_OK;
+}
+
+gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, const float* positions, const float* normals) {
+    if (!ctx) return GBL_ERR_INVALID;
+    gbl_status st = check_edit_range(ctx, mesh, first, count, positions);
+    if (st != GBL_OK) return st;
+    const gbl_mesh& gm = ctx->h_meshes[mesh];
+    for (size_t i = 0; i < 3 * static_cast<size_t>(count); ++i)
+        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) return fail_not_finite(ctx, first, i, !std::isfinite(positions[i]));
+    if ((st = check_edit_allowed(ctx, mesh, normals != nullptr)) != GBL_OK) return st;
     const auto now = [] { return std::chrono::steady_clock::now(); };
     const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t0 = now();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables
-    gbl_status st = ensure_plan(ctx, mesh);
-    if (st != GBL_OK) return st;
+    if ((st = ensure_plan(ctx, mesh)) != GBL_OK) return st;
+    if ((st = refresh_mirror(ctx, mesh)) != GBL_OK) return st;   // (a device edit may have left the mirror behind: the patch goes onto the current positions)
     const gbl_ctx::MeshRefit& mr = ctx->refit[mesh];
     DevScene& sc = ctx->scene;
     const size_t v0 = static_cast<size_t>(gm.vertex_offset) + first, floats = 3 * static_cast<size_t>(count);
@@ -82,22 +158,14 @@ gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first,
         HIP_TRY(ctx, hipMemcpy(const_cast<float*>(sc.positions) + 3 * v0, positions, floats * sizeof(float), hipMemcpyHostToDevice));
         if (normals) HIP_TRY(ctx, hipMemcpy(const_cast<float*>(sc.normals) + 3 * v0, normals, floats * sizeof(float), hipMemcpyHostToDevice));
     }
-    // triangles and their bounds, then the nodes from the deepest level to the root (the stream orders the launches)
-    gbl_launch_refit_tris(const_cast<DevTri*>(sc.tris), const_cast<DevTriBound*>(sc.tri_bounds), sc.tri_shade, sc.positions,
-                          static_cast<uint32_t>(ctx->h_positions.size() / 3), ctx->mesh_tri_first[mesh], gm.tri_count, 0);
-    for (size_t l = mr.level_first.size(); l-- > 1;)
-        gbl_launch_refit_level(const_cast<DevNode*>(sc.nodes), sc.tri_bounds, mr.plan, mr.node_box, mr.level_first[l - 1], mr.level_first[l], 0);
+    launch_refit(ctx, mesh);
     HIP_TRY(ctx, hipGetLastError());
     const auto t1 = now();
     // while the device works: the reference's visiting order over the edited positions (what exact_ties, replay, stream and the
     // EXT builds break ties by), and the mesh's object bound
-    const float* mesh_pos = ctx->h_positions.data() + 3 * static_cast<size_t>(gm.vertex_offset);
-    std::vector<DevTriOrder> order(gm.tri_count);
-    mesh_reference_order(mesh_pos, ctx->h_indices.data() + 3 * static_cast<size_t>(gm.tri_offset), gm.tri_count, order.data());
-    if (!order.empty())
-        HIP_TRY(ctx, hipMemcpy(const_cast<DevTriOrder*>(sc.tri_order) + gm.tri_offset, order.data(), order.size() * sizeof(DevTriOrder), hipMemcpyHostToDevice));
+    if ((st = make_order(ctx, mesh)) != GBL_OK) return st;
     const auto t2 = now();
-    mesh_object_bound(mesh_pos, gm.vertex_count, &ctx->mesh_lo[3 * mesh], &ctx->mesh_hi[3 * mesh]);
+    mesh_object_bound(ctx->h_positions.data() + 3 * static_cast<size_t>(gm.vertex_offset), gm.vertex_count, &ctx->mesh_lo[3 * mesh], &ctx->mesh_hi[3 * mesh]);
     std::vector<gbl_instance> instances = ctx->h_instances;
     st = rebuild_tlas(ctx, instances, "gbl_update_vertices");   // (synchronises before its uploads, and clears the AUTO pilot)
     if (st != GBL_OK) return st;
@@ -109,11 +177,113 @@ gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first,
     return GBL_OK;
 }
 
-gbl_status gbl_get_vertices_impl(const gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* positions_out) {
-    if (!ctx || !positions_out || mesh >= ctx->h_meshes.size()) return GBL_ERR_INVALID;
+// gbl_update_vertices over device memory.  Every refusal the host can make comes first; the finiteness check is the one launch
+// ahead of the context's first change.
+gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, const float* d_positions, const float* d_normals,
+                                           uint32_t flags) {
+    if (!ctx) return GBL_ERR_INVALID;
+    gbl_status st = check_edit_range(ctx, mesh, first, count, d_positions);
+    if (st != GBL_OK) return st;
+    if (flags & ~GBL_VERTICES_DEFER_ORDER) return fail(ctx, GBL_ERR_INVALID, "gbl_update_vertices_device: unknown bits in flags");
+    if ((st = check_edit_allowed(ctx, mesh, d_normals != nullptr)) != GBL_OK) return st;
+    const gbl_mesh& gm = ctx->h_meshes[mesh];
+    const uint64_t floats = 3 * static_cast<uint64_t>(count);
+    if (3 * static_cast<uint64_t>(gm.vertex_count) >= 0xFFFFFFFFull)
+        return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_vertices_device: a mesh of 2^32 / 3 vertices or more (the check word holds a float's index)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((st = check_device_pointer(ctx, d_positions, floats * sizeof(float), "gbl_update_vertices_device", "d_positions")) != GBL_OK) return st;
+    if (d_normals && (st = check_device_pointer(ctx, d_normals, floats * sizeof(float), "gbl_update_vertices_device", "d_normals")) != GBL_OK) return st;
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
+    if (!ctx->vertex_words.p && (st = grow(ctx, ctx->vertex_words, GBL_VW_BYTES, "vertex edit words")) != GBL_OK) return st;
+    unsigned char* words = static_cast<unsigned char*>(ctx->vertex_words.p);
+    HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables, and whatever wrote the caller's floats is done
+    HIP_TRY(ctx, hipMemsetAsync(words, 0xFF, GBL_VW_FILL, 0));
+    if (count > 0) {
+        uint32_t bad = 0xFFFFFFFFu;
+        gbl_launch_vertices_check(d_positions, d_normals, static_cast<uint32_t>(floats), reinterpret_cast<uint32_t*>(words + GBL_VW_CHECK), 0);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpy(&bad, words + GBL_VW_CHECK, sizeof(bad), hipMemcpyDeviceToHost));
+        if (bad != 0xFFFFFFFFu) {   // which of the two at that index: a position comes before a normal
+            if (bad >= floats) return fail(ctx, GBL_ERR_INTERNAL, "gbl_update_vertices_device: the check word is out of range");
+            float v = 0.0f;
+            HIP_TRY(ctx, hipMemcpy(&v, d_positions + bad, sizeof(v), hipMemcpyDeviceToHost));
+            return fail_not_finite(ctx, first, bad, !std::isfinite(v));
+        }
+    }
+    const auto t1 = now();
+    if ((st = ensure_plan(ctx, mesh)) != GBL_OK) return st;
+    DevScene& sc = ctx->scene;
+    const size_t m0 = 3 * static_cast<size_t>(gm.vertex_offset), v0 = m0 + 3 * static_cast<size_t>(first);
+    if (ctx->mirror_stale.size() != ctx->h_meshes.size()) ctx->mirror_stale.assign(ctx->h_meshes.size(), 0);
+    if (ctx->order_pending.size() != ctx->h_meshes.size()) ctx->order_pending.assign(ctx->h_meshes.size(), 0);
+    if (count > 0) {
+        ctx->mirror_stale[mesh] = 1;
+        HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(sc.positions) + v0, d_positions, floats * sizeof(float), hipMemcpyDeviceToDevice, 0));
+        if (d_normals) HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(sc.normals) + v0, d_normals, floats * sizeof(float), hipMemcpyDeviceToDevice, 0));
+    }
+    launch_refit(ctx, mesh);
+    gbl_launch_mesh_bound(sc.positions + m0, gm.vertex_count, reinterpret_cast<unsigned long long*>(words + GBL_VW_KEYS), reinterpret_cast<float*>(words + GBL_VW_BOUND), 0);
+    HIP_TRY(ctx, hipGetLastError());
+    const auto t2 = now();
+    // the tie order: now, on the host over the refreshed mirror (while the device works), or left to its first reader
+    if (flags & GBL_VERTICES_DEFER_ORDER) {
+        if (!ctx->order_pending[mesh]) {
+            ctx->order_pending[mesh] = 1;
+            ctx->orders_pending += 1;
+        }
+    } else {
+        if ((st = refresh_mirror(ctx, mesh)) != GBL_OK) return st;
+        if ((st = make_order(ctx, mesh)) != GBL_OK) return st;
+    }
+    const auto t3 = now();
+    float bound[6];
+    HIP_TRY(ctx, hipMemcpy(bound, words + GBL_VW_BOUND, sizeof(bound), hipMemcpyDeviceToHost));
+    for (int a = 0; a < 3; ++a) ctx->mesh_lo[3 * mesh + a] = bound[a], ctx->mesh_hi[3 * mesh + a] = bound[3 + a];
+    std::vector<gbl_instance> instances = ctx->h_instances;
+    st = rebuild_tlas(ctx, instances, "gbl_update_vertices_device");   // (synchronises before its uploads, and clears the AUTO pilot)
+    if (st != GBL_OK) return st;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (getenv("GBL_PROBE"))
+        fprintf(stderr, "probe: gbl_update_vertices_device mesh %u (%u triangles, flags %u): synchronise, check and its word %.3f ms, plan, copies and launches %.3f ms, "
+                        "tri_order %.3f ms, bound read-back and TLAS %.3f ms\n", mesh, gm.tri_count, flags, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
+    return GBL_OK;
+}
+
+gbl_status gbl_get_vertices_impl(const gbl_ctx* cctx, uint32_t mesh, uint32_t first, uint32_t count, float* positions_out) {
+    if (!cctx || !positions_out || mesh >= cctx->h_meshes.size()) return GBL_ERR_INVALID;
+    gbl_ctx* ctx = const_cast<gbl_ctx*>(cctx);   // (the mirror is a cache of the device's positions: refreshing it changes nothing a caller can see)
     const gbl_mesh& gm = ctx->h_meshes[mesh];
     if (gm.shape != GBL_SHAPE_MESH || static_cast<uint64_t>(first) + count > gm.vertex_count) return GBL_ERR_INVALID;
+    const gbl_status st = refresh_mirror(ctx, mesh);
+    if (st != GBL_OK) return st;
     if (count > 0) memcpy(positions_out, ctx->h_positions.data() + 3 * (static_cast<size_t>(gm.vertex_offset) + first), 3 * static_cast<size_t>(count) * sizeof(float));
+    return GBL_OK;
+}
+
+gbl_status gbl_get_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* d_positions_out) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!d_positions_out) return fail(ctx, GBL_ERR_INVALID, "gbl_get_vertices_device: d_positions_out is NULL");
+    if (mesh >= ctx->h_meshes.size()) return fail(ctx, GBL_ERR_INVALID, "gbl_get_vertices_device: mesh " + std::to_string(mesh) + " is out of range");
+    const gbl_mesh& gm = ctx->h_meshes[mesh];
+    if (gm.shape != GBL_SHAPE_MESH) return fail(ctx, GBL_ERR_INVALID, "gbl_get_vertices_device: mesh " + std::to_string(mesh) + " is a sphere or a disk: it has no vertices");
+    if (static_cast<uint64_t>(first) + count > gm.vertex_count) return fail(ctx, GBL_ERR_INVALID, "gbl_get_vertices_device: vertex range out of bounds");
+    const uint64_t bytes = 3 * static_cast<uint64_t>(count) * sizeof(float);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const gbl_status st = check_device_pointer(ctx, d_positions_out, bytes, "gbl_get_vertices_device", "d_positions_out");
+    if (st != GBL_OK) return st;
+    // the positions change only inside calls that synchronise, so the null stream's order is all the copy needs
+    if (count > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_positions_out, ctx->scene.positions + 3 * (static_cast<size_t>(gm.vertex_offset) + first), bytes, hipMemcpyDeviceToDevice, 0));
+        HIP_TRY(ctx, hipStreamSynchronize(0));
+    }
+    return GBL_OK;
+}
+
+gbl_status gbl_order_pending_impl(const gbl_ctx* ctx, uint32_t mesh, uint32_t* pending) {
+    if (!ctx || !pending || mesh >= ctx->h_meshes.size()) return GBL_ERR_INVALID;
+    *pending = mesh < ctx->order_pending.size() && ctx->order_pending[mesh] ? 1u : 0u;
     return GBL_OK;
 }
 
@@ -135,11 +305,28 @@ gbl_status gbl_selftest_geometry_impl(gbl_ctx* ctx, int table, uint64_t first, u
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
+    if (table == 3) {   // a reader of the tie order
+        const gbl_status st = make_orders_if(ctx, true);
+        if (st != GBL_OK) return st;
+    }
     HIP_TRY(ctx, hipMemcpy(out, static_cast<const unsigned char*>(base[table]) + first * size[table], count * size[table], hipMemcpyDeviceToHost));
     return GBL_OK;
 }
 
 }   // namespace
+
+gbl_status make_pending_orders(gbl_ctx* ctx) {
+    if (ctx->orders_pending == 0) return GBL_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // no launch in flight may be reading the table
+    for (uint32_t mesh = 0; mesh < ctx->order_pending.size(); ++mesh) {
+        if (!ctx->order_pending[mesh]) continue;
+        gbl_status st = refresh_mirror(ctx, mesh);
+        if (st == GBL_OK) st = make_order(ctx, mesh);
+        if (st != GBL_OK) return st;
+    }
+    return GBL_OK;
+}
 
 extern "C" {
 
@@ -149,6 +336,19 @@ gbl_status gbl_update_vertices(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint
 
 gbl_status gbl_get_vertices(const gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* positions_out) {
     return gbl_guard([&] { return gbl_get_vertices_impl(ctx, mesh, first, count, positions_out); }, [&](const std::string&) {});
+}
+
+gbl_status gbl_update_vertices_device(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, const float* d_positions, const float* d_normals, uint32_t flags) {
+    return gbl_guard([&] { return gbl_update_vertices_device_impl(ctx, mesh, first, count, d_positions, d_normals, flags); },
+                     [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+gbl_status gbl_get_vertices_device(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* d_positions_out) {
+    return gbl_guard([&] { return gbl_get_vertices_device_impl(ctx, mesh, first, count, d_positions_out); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+gbl_status gbl_order_pending(const gbl_ctx* ctx, uint32_t mesh, uint32_t* pending) {
+    return gbl_guard([&] { return gbl_order_pending_impl(ctx, mesh, pending); }, [&](const std::string&) {});
 }
 
 gbl_status gbl_selftest_geometry(gbl_ctx* ctx, int table, uint64_t first, uint64_t count, void* out, uint64_t* total) {

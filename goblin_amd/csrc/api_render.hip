@@ -91,6 +91,10 @@ struct Plan : SamplePlan {
     StreamLayout layout;        // GBL_SAMPLES_STREAM: the sample quota of a pixel
     bool wavefront = false;     // choose_schedule
     int pass_spp = 0;           // ... wavefront: samples per pixel of one pass
+    // choose_flavours: which builds the call launches, decided once
+    bool vol_pass = false, sss_pass = false;   // the first-hit passes (first_hit_passes)
+    bool lean_native = false;   // the integrator's kernels are the native sampler's lean builds: no tie rule (trace.h)
+    bool follows_ties = false;  // some kernel of the call is compiled with the tie rule and reads tri_order (make_orders_if)
 };
 
 // LDS of the film tile the splat accumulates into
@@ -217,8 +221,7 @@ gbl_status render_wavefront(gbl_ctx* ctx, const gbl_render_params* p, const Plan
     // build.  Instrumented launches always use the EXT build (same work, same counters).
     const bool ext = sc.extended != 0;
     const bool masks = sc.has_masks != 0;
-    // native sampler, lean build: no tie rule (trace.h)
-    const bool lean_native = !ext && !masks && !want_stats && !replay && p->exact_ties == 0;
+    const bool lean_native = pl.lean_native;   // native sampler, lean build: no tie rule (choose_flavours)
     gbl_wf_kernel k_ext = gbl_kernel_wf_trace(false, want_stats, ext || masks || want_stats, masks, !lean_native);
     gbl_wf_kernel k_shd = gbl_kernel_wf_trace(true, want_stats, ext || masks || want_stats, masks, !lean_native);
     // persistent trace grids: exactly the resident workgroups (regions are assigned statically, so a
@@ -678,6 +681,21 @@ dim3 sample_grid(const gbl_ctx* ctx, const RenderArgs& ra) {
     return dim3(static_cast<unsigned>(std::min<uint64_t>((total + GBL_BLOCK - 1) / GBL_BLOCK, static_cast<uint64_t>(ctx->num_cus) * 8)));
 }
 
+// Which builds the call launches, once the schedule is chosen: the first-hit passes, and whether the integrator's kernels are
+// the lean ones of the native sampler.  The lean builds compile the tie rule out; every other build reads tri_order: the EXT,
+// replay, stream, instrumented and exact_ties builds of the path tracer and AO (render_kernels.h TIES = REPLAY || STATS || EXACT ||
+// EXT, which gbl_kernel_path / gbl_kernel_ao and the quad selectors instantiate from the same four facts), the wavefront trace
+// kernels for those and for alpha masks (render_wavefront), the Whitted kernels and both first-hit passes (trace<> with its
+// default TIES).  render_wavefront takes lean_native from here and the first-hit passes their conditions, so what gbl_render
+// makes a pending tie order for is what it launches.
+void choose_flavours(const gbl_ctx* ctx, const gbl_render_params* p, Plan& pl) {
+    const DevScene& sc = ctx->scene;
+    pl.vol_pass = sc.volume.on != 0u && !pl.stream_mode;
+    pl.sss_pass = sc.has_bssrdf != 0 && p->integrator == GBL_INTEGRATOR_PATH && !pl.stream_mode;
+    pl.lean_native = sc.extended == 0 && !(pl.wavefront && sc.has_masks != 0) && !pl.want_stats && !pl.replay && p->exact_ties == 0;
+    pl.follows_ties = pl.whitted || pl.vol_pass || pl.sss_pass || !pl.lean_native;
+}
+
 // Passes over every camera sample's first hit, ahead of the integrator kernel (not under GBL_SAMPLES_STREAM, whose integrator
 // kernels do this per pixel: the medium's draws follow each sample's Li draws in the tile's stream, stream_medium_phase):
 // - the participating medium's {tr, Lv} (kernels/volume.h); the splat applies them;
@@ -687,7 +705,7 @@ gbl_status first_hit_passes(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl, 
     RenderArgs& ra = pl.ra;
     const size_t lds = stack_lds_bytes(sc);
     gbl_status st;
-    if (sc.volume.on != 0u && !pl.stream_mode) {
+    if (pl.vol_pass) {
         if ((st = grow(ctx, ctx->vol, pl.entries * 2 * sizeof(float4), "medium terms")) != GBL_OK) return st;
         ra.vol = static_cast<float*>(ctx->vol.p);
         gbl_render_kernel k_vol = gbl_kernel_vol(pl.replay);
@@ -695,7 +713,7 @@ gbl_status first_hit_passes(gbl_ctx* ctx, const gbl_render_params* p, Plan& pl, 
         hipLaunchKernelGGL(k_vol, sample_grid(ctx, ra), dim3(GBL_BLOCK), lds, stream, sc, ra);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (sc.has_bssrdf != 0 && p->integrator == GBL_INTEGRATOR_PATH && !pl.stream_mode) {
+    if (pl.sss_pass) {
         if ((st = grow(ctx, ctx->sss, pl.entries * sizeof(float4), "subsurface term")) != GBL_OK) return st;
         float4* sss = static_cast<float4*>(ctx->sss.p);
         ra.sss = reinterpret_cast<const float*>(sss);
@@ -971,6 +989,8 @@ gbl_status gbl_render_impl(gbl_ctx* ctx, const gbl_render_params* p, float* film
     float rays_per_path = 0.0f;
     if ((st = auto_pilot(ctx, p, pl, knobs, &rays_per_path)) != GBL_OK) return st;
     if ((st = choose_schedule(ctx, p, rays_per_path, pl)) != GBL_OK) return st;
+    choose_flavours(ctx, p, pl);
+    if ((st = make_orders_if(ctx, pl.follows_ties)) != GBL_OK) return st;   // a deferred vertex edit's tie order, for its first reader
 
     hipStream_t stream = static_cast<hipStream_t>(p->stream);
     HIP_TRY(ctx, hipSetDevice(ctx->device));

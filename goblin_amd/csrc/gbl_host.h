@@ -22,6 +22,21 @@ gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what);
 // error messages.  A refusal (build_tlas's, or a TLAS beyond the reserved nodes) leaves the context untouched.  (api_context.hip)
 gbl_status rebuild_tlas(gbl_ctx* ctx, std::vector<gbl_instance>& instances, const char* who);
 
+// The tie order of every mesh a deferred device edit left pending (gbl_update_vertices_device with GBL_VERTICES_DEFER_ORDER):
+// mirror refreshed, mesh_reference_order on the host, the mesh's tri_order slice uploaded, behind a device synchronisation.
+// Every entry point calls it where it has chosen a kernel compiled with the tie rule, before it queues anything, and no
+// other: a lean launch leaves the orders pending.  Nothing to do (and nothing synchronised) when none is.  (api_geometry.hip)
+gbl_status make_pending_orders(gbl_ctx* ctx);
+inline gbl_status make_orders_if(gbl_ctx* ctx, bool follows_ties) { return follows_ties && ctx->orders_pending > 0 ? make_pending_orders(ctx) : GBL_OK; }
+
+// The mesh's slice of h_positions brought up to the device's, if a device edit left it stale: one device-to-host copy.  The
+// caller has synchronised the device or knows it idle.  (api_geometry.hip)
+gbl_status refresh_mirror(gbl_ctx* ctx, uint32_t mesh);
+
+// GBL_OK when `p` is device or managed memory of the context's device whose allocation holds `bytes` from p on; GBL_ERR_INVALID
+// with "`who`: `what` ..." otherwise, the sticky error a plain host pointer leaves cleared.  Touches no device memory.  (api_geometry.hip)
+gbl_status check_device_pointer(gbl_ctx* ctx, const void* p, uint64_t bytes, const std::string& who, const char* what);
+
 // A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it first
 template <class K>
 gbl_status allow_lds(gbl_ctx* ctx, K kernel, size_t bytes) {

@@ -18,6 +18,7 @@
 #include "kernels/temporal_args.h"
 #include "kernels/motion_args.h"
 #include "kernels/refit_args.h"
+#include "kernels/vertices_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -100,6 +101,12 @@ struct gbl_ctx {
         RefitBox* node_box = nullptr;        // ... and a box per record
     };
     std::vector<MeshRefit> refit;            // per mesh, built at its first edit
+    // what the device-pointer entries add (gbl_update_vertices_device, gbl_render_motion_deform_device; kernels/vertices.h)
+    std::vector<unsigned char> mirror_stale;    // per mesh: the device positions are newer than the mesh's slice of h_positions (refresh_mirror)
+    std::vector<unsigned char> order_pending;   // per mesh: its tri_order slice waits for its first reader (make_pending_orders)
+    uint32_t orders_pending = 0;                // ... how many are set
+    gbl_buf vertex_words;     // six 64-bit keys and the check word (64 bytes, all ones before a call's launches), then the bound's six floats
+    gbl_buf pose_words;       // gbl_render_motion_deform_device: per listed mesh a check word, a differs flag and its PoseList record
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
@@ -187,6 +194,12 @@ void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade*
                            uint32_t count, hipStream_t stream);
 void gbl_launch_refit_level(DevNode* nodes, const DevTriBound* bounds, const RefitRecord* plan, RefitBox* node_box, uint32_t begin, uint32_t end,
                             hipStream_t stream);
+// kernels_vertices.hip: the passes of the device-pointer vertex entries (kernels/vertices.h).  first_bad, keys and differs are
+// set by the caller before the launch (all ones, all ones, zero); `list` holds num_listed PoseList records on the device
+void gbl_launch_vertices_check(const float* positions, const float* normals, uint32_t n, uint32_t* first_bad, hipStream_t stream);
+void gbl_launch_mesh_bound(const float* positions, uint32_t vertex_count, unsigned long long* keys, float* bound, hipStream_t stream);
+void gbl_launch_pose_differs(const PoseList* list, uint32_t num_listed, uint32_t max_floats, const float* positions, uint32_t num_floats_total, uint32_t* differs,
+                             hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);

@@ -3,7 +3,7 @@
 // of the C ABI.
 #include "abi_guard.h"
 #include <chrono>
-#include "gbl_internal.h"
+#include "gbl_host.h"
 #include "kernels/render_kernels.h"
 #include "kernels/subsurface.h"
 #include "kernels/volume.h"
@@ -337,6 +337,8 @@ static gbl_status gbl_selftest_trace_impl(gbl_ctx* ctx, const float* rays, float
     if (!ctx || !rays || !out) return GBL_ERR_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n == 0) return GBL_OK;
+    const gbl_status st = make_orders_if(ctx, true);   // (the kernel traces with the tie rule)
+    if (st != GBL_OK) return st;
     const size_t lds = static_cast<size_t>(ctx->scene.stack_entries) * GBL_BLOCK * sizeof(uint32_t);
     if (lds > 64 * 1024)
         HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(selftest_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -91,10 +91,52 @@ class HipPathTracer:
             raise _abi.GoblinError(st, "gbl_get_instances")
         return [(tuple(arr[i].position), tuple(arr[i].orientation), tuple(arr[i].scale)) for i in range(n)]
 
-    def update_vertices(self, mesh, positions, normals=None, first=0):
+    def _device_vertices(self, what, t, shape=None):
+        """The data pointer of ``t``, a contiguous float32 (n, 3) tensor on the tracer's device (its storage offset included);
+        ValueError for anything else.  An empty tensor has no pointer of its own and borrows one."""
+        torch = _torch()
+        if t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 (n, 3) tensor on %s, got %s %s on %s%s" %
+                             (what, self.device, t.dtype, tuple(t.shape), t.device, "" if t.is_contiguous() else ", not contiguous"))
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(t.shape)))
+        if t.shape[0] == 0:
+            self._one_vertex = getattr(self, "_one_vertex", None)
+            if self._one_vertex is None:
+                self._one_vertex = torch.zeros((1, 3), dtype=torch.float32, device=self.device)
+            return self._one_vertex.data_ptr()
+        return t.data_ptr()
+
+    def update_vertices(self, mesh, positions, normals=None, first=0, defer_order=False):
         """Give vertices first.. of triangle mesh ``mesh`` (its index in the scene's meshes) new object-space positions -- an (n, 3)
         float32 array -- and, with ``normals``, new vertex normals; the mesh's BLAS is refitted on the device in place
-        (gbl_update_vertices).  The topology stays; without ``normals`` the vertex normals stay as they were."""
+        (gbl_update_vertices).  The topology stays; without ``normals`` the vertex normals stay as they were.
+
+        A contiguous float32 (n, 3) torch tensor on the tracer's device is read where it lies (gbl_update_vertices_device; a
+        slice with a storage offset is fine); any other tensor is a ValueError.  ``defer_order``: leave the mesh's tie order --
+        7.6 ms on the host for the bunny, read only by exact_ties, replay, stream, instrumented and Whitted renders and by
+        scenes beyond the headline feature set -- to the first call that needs it (``order_pending``); arrays are uploaded to
+        a tensor first then."""
+        is_tensor = [hasattr(x, "data_ptr") for x in (positions, normals) if x is not None]
+        if any(is_tensor) or defer_order:
+            torch = _torch()
+            if any(is_tensor) and not all(is_tensor):
+                raise ValueError("positions and normals must both be tensors or both be arrays")
+            if not is_tensor[0]:
+                pos = np.ascontiguousarray(positions, np.float32)
+                if pos.ndim != 2 or pos.shape[1] != 3:
+                    raise ValueError("positions must have shape (n, 3), got %s" % (pos.shape,))
+                positions = torch.from_numpy(pos).to(self.device)
+                if normals is not None:
+                    normals = torch.from_numpy(np.ascontiguousarray(normals, np.float32)).to(self.device)
+            p_ptr = self._device_vertices("positions", positions)
+            n_ptr = self._device_vertices("normals", normals, positions.shape) if normals is not None else None
+            st = self.lib.gbl_update_vertices_device(self.handle, int(mesh), int(first), positions.shape[0], p_ptr, n_ptr,
+                                                     _abi.GBL_VERTICES_DEFER_ORDER if defer_order else 0)
+            if st != _abi.GBL_OK:
+                raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+            self.lib.gbl_get_info(self.handle, C.byref(self.info))
+            return
         pos = np.ascontiguousarray(positions, np.float32)
         if pos.ndim != 2 or pos.shape[1] != 3:
             raise ValueError("positions must have shape (n, 3), got %s" % (pos.shape,))
@@ -108,15 +150,32 @@ class HipPathTracer:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         self.lib.gbl_get_info(self.handle, C.byref(self.info))
 
-    def vertices(self, mesh):
+    def vertices(self, mesh, device=False):
         """The positions the context holds now for triangle mesh ``mesh`` (gbl_get_vertices): (vertex_count, 3) float32 -- the
-        scene's at first, the edited ones after ``update_vertices``."""
+        scene's at first, the edited ones after ``update_vertices``.  ``device=True``: a tensor on the tracer's device, copied
+        device to device (gbl_get_vertices_device) -- what ``motion`` takes as ``prev_vertices`` without a trip to the host."""
         n = int(self.scene.desc.meshes[int(mesh)].vertex_count) if 0 <= int(mesh) < self.scene.desc.num_meshes else 0
+        if device:
+            torch = _torch()
+            out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)
+            st = self.lib.gbl_get_vertices_device(self.handle, int(mesh), 0, n, out.data_ptr())
+            if st != _abi.GBL_OK:
+                raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+            return out[:n]
         out = np.empty((n, 3), np.float32)
         st = self.lib.gbl_get_vertices(self.handle, int(mesh), 0, n, out.ctypes.data)
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, "gbl_get_vertices")
         return out
+
+    def order_pending(self, mesh):
+        """1 while the tie order of ``mesh`` waits for its first reader after ``update_vertices(..., defer_order=True)``, else 0
+        (gbl_order_pending)."""
+        pending = C.c_uint32()
+        st = self.lib.gbl_order_pending(self.handle, int(mesh), C.byref(pending))
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, "gbl_order_pending")
+        return int(pending.value)
 
     _GEOMETRY = (np.dtype([("o", "<f4", 3), ("scale", "<f4", 3), ("qlo", "<u4", 3), ("qhi", "<u4", 3), ("child", "<i4", 4)]),
                  np.dtype([("p0", "<f4", 3), ("shade", "<u4"), ("e1", "<f4", 3), ("flags", "<u4"), ("e2", "<f4", 3), ("pad1", "<f4")]),
@@ -402,7 +461,9 @@ class HipPathTracer:
         + 1 or 0}, the normal taken from ``normal`` (render_aov's film; zeros without one).  ``accumulate(motion=...)`` reads it.
         ``prev_vertices``: {mesh: (vertex_count, 3) float32 array}, ``vertices(mesh)`` as it was when the previous frame was
         rendered, for every mesh ``update_vertices`` edited since (gbl_render_motion_deform): a surface that deformed is followed
-        through its triangle's previous pose.  A mesh whose positions are the context's own counts as not deformed."""
+        through its triangle's previous pose.  A mesh whose positions are the context's own counts as not deformed.  Tensors on
+        the tracer's device (``vertices(mesh, device=True)``) are read where they lie (gbl_render_motion_deform_device); a dict
+        that mixes tensors and arrays is a ValueError."""
         torch = _torch()
         h, w = self.info.yres, self.info.xres
         p = _abi.gbl_motion_params()
@@ -429,18 +490,27 @@ class HipPathTracer:
         else:
             keep = []       # the arrays the list points into, alive across the call
             listed = (_abi.gbl_motion_mesh * max(len(prev_vertices), 1))()
+            on_device = [hasattr(v, "data_ptr") for v in prev_vertices.values()]
+            if any(on_device) and not all(on_device):
+                raise ValueError("prev_vertices must hold tensors only or arrays only")
             for k, (mesh, positions) in enumerate(prev_vertices.items()):
                 mesh = int(mesh)
-                pos = np.ascontiguousarray(positions, np.float32)
-                if 0 <= mesh < self.scene.desc.num_meshes and self.scene.desc.meshes[mesh].shape == 0:
-                    count = int(self.scene.desc.meshes[mesh].vertex_count)
-                    if pos.shape != (count, 3):
-                        raise ValueError("prev_vertices[%d] must have shape (%d, 3), got %s" % (mesh, count, pos.shape))
-                elif mesh < 0:
+                known = 0 <= mesh < self.scene.desc.num_meshes and self.scene.desc.meshes[mesh].shape == 0
+                count = int(self.scene.desc.meshes[mesh].vertex_count) if known else None
+                if mesh < 0:
                     raise ValueError("prev_vertices: mesh %d is out of range" % mesh)
-                keep.append(pos)
-                listed[k].mesh, listed[k].reserved, listed[k].positions = mesh, 0, pos.ctypes.data
-            st = self.lib.gbl_render_motion_deform(self.handle, C.byref(p), listed, len(prev_vertices), out.data_ptr())
+                if all(on_device):
+                    ptr = self._device_vertices("prev_vertices[%d]" % mesh, positions, (count, 3) if known else None)
+                    keep.append(positions)
+                else:
+                    pos = np.ascontiguousarray(positions, np.float32)
+                    if known and pos.shape != (count, 3):
+                        raise ValueError("prev_vertices[%d] must have shape (%d, 3), got %s" % (mesh, count, pos.shape))
+                    keep.append(pos)
+                    ptr = pos.ctypes.data
+                listed[k].mesh, listed[k].reserved, listed[k].positions = mesh, 0, ptr
+            entry = self.lib.gbl_render_motion_deform_device if prev_vertices and all(on_device) else self.lib.gbl_render_motion_deform
+            st = entry(self.handle, C.byref(p), listed, len(prev_vertices), out.data_ptr())
             del keep
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())

@@ -667,6 +667,15 @@ typedef struct gbl_motion_mesh {
 } gbl_motion_mesh;
 gbl_status gbl_render_motion_deform(gbl_ctx* ctx, const gbl_motion_params* params, const gbl_motion_mesh* prev_meshes,
                                     uint32_t num_prev_meshes, float* motion_out);
+/* gbl_render_motion_deform with every gbl_motion_mesh::positions pointing to DEVICE memory (gbl_get_vertices_device before the
+ * edit): the same planes bit for bit, the same refusals in the same order, and for each positions pointer the two pointer
+ * refusals of gbl_update_vertices_device.  Finiteness is checked by a kernel, and which listed meshes are deformed is decided by
+ * another, bitwise against the positions the device holds; one word per listed mesh is read back for each, behind a wait for
+ * params->stream (the choice of kernel depends on the answer).  The deformed meshes' previous positions are copied device to
+ * device into the context's table on params->stream; whatever writes the caller's arrays next must be ordered behind that
+ * stream.  No tie order is made (see gbl_update_vertices_device): none of gbl_render_motion's kernels reads it. */
+gbl_status gbl_render_motion_deform_device(gbl_ctx* ctx, const gbl_motion_params* params, const gbl_motion_mesh* prev_meshes /* .positions: device */,
+                                           uint32_t num_prev_meshes, float* motion_out);
 
 /* gbl_film_accumulate with the reprojection read from `motion` (gbl_render_motion's planes for this frame) instead of
  * computed from the depth film and params->prev_camera, which is not read: (image_x, image_y, z_exp) = M0.xyz, a pixel with
@@ -739,9 +748,45 @@ gbl_status gbl_get_instances(const gbl_ctx* ctx, uint32_t first, uint32_t count,
  * scene bound it carries is read by those two kinds of light only.)  positions and normals are host pointers. */
 gbl_status gbl_update_vertices(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count,
                                const float* positions /* host, 3 * count */, const float* normals /* host, 3 * count, or NULL */);
-/* The positions the context holds now (gbl_create's at first).  Host only, like gbl_get_instances.  GBL_ERR_INVALID for a NULL
- * argument, a mesh out of range or not a triangle mesh, a range out of bounds. */
+/* The positions the context holds now (gbl_create's at first).  Host only, like gbl_get_instances, but for the first call after a
+ * gbl_update_vertices_device of the mesh, which downloads the mesh's positions once.  GBL_ERR_INVALID for a NULL argument, a mesh
+ * out of range or not a triangle mesh, a range out of bounds. */
 gbl_status gbl_get_vertices(const gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* positions_out);
+
+/* gbl_update_vertices with positions and normals read from DEVICE memory: what a skinning or morphing step on the GPU leaves
+ * behind goes into the context without a trip through the host.  After the call every device table -- nodes, triangles, their
+ * bounds, positions, normals, instance records and bounds, the TLAS, and the tie order unless deferred -- is byte for byte what
+ * gbl_update_vertices leaves when fed the same floats.
+ *  - Order of the call: synchronise; the finiteness check (a kernel; 4 bytes read back); the refit plan on the mesh's first edit;
+ *    device-to-device copies; gbl_update_vertices' refit launches; the mesh's object bound on the device (24 bytes read back); the
+ *    TLAS on the host as in every edit; synchronise.  Nothing else crosses the bus.
+ *  - The context's host copy of the positions becomes a mirror: the edit marks the mesh's slice stale, and gbl_get_vertices,
+ *    gbl_update_vertices, gbl_render_motion_deform and the tie order refresh it with one download of the slice when they need it.
+ *  - The tie order (the reference's visiting order, what exact ties are broken by) is made on the host from the mirror, as
+ *    gbl_update_vertices makes it: about 7.6 ms for the bunny's 69 451 triangles, beside 0.2 ms for everything else.  Only the
+ *    kernels compiled with the tie rule read it: replay, stream, instrumented and exact_ties renders, Whitted, and every kernel of
+ *    a scene beyond the headline feature set (the EXT builds).  With GBL_VERTICES_DEFER_ORDER the mesh is marked pending instead
+ *    (gbl_order_pending), and the first call that launches such a kernel -- gbl_render, gbl_render_aov, gbl_selftest_trace -- or
+ *    reads the table (gbl_selftest_geometry table 3), or a gbl_update_vertices of the mesh, makes the order of every pending
+ *    mesh before it queues anything (one more synchronisation).  A call that launches lean kernels only -- gbl_render under the
+ *    native sampler without exact_ties and collect_stats, gbl_render_aov likewise, every gbl_render_motion* -- leaves it pending
+ *    and never pays for it.  (GBL_SCHEDULE_AUTO's pilot after an edit is an instrumented render: it makes the order.)
+ *    What deferral buys: a frame loop on a lean scene edits in 0.2 ms instead of 7.8.  What it does not: the cost is moved, not
+ *    removed -- a scene that needs the EXT kernels pays the same 7.6 ms inside its next render.
+ * Refusals, the context untouched: gbl_update_vertices' own with its messages (the host-side ones first; a non-finite coordinate
+ * is met last, by the kernel, with the host entry's message: the lowest float index decides, a position before a normal), and
+ * GBL_ERR_INVALID for unknown bits in flags, for a pointer that is not device or managed memory of the context's device (a
+ * plain host pointer is refused before anything reads it), and for one whose allocation ends before 12 * count bytes. */
+#define GBL_VERTICES_DEFER_ORDER 1u
+gbl_status gbl_update_vertices_device(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, const float* d_positions /* device, 3 * count */,
+                                      const float* d_normals /* device, 3 * count, or NULL */, uint32_t flags);
+/* gbl_get_vertices into DEVICE memory: a device-to-device copy of the positions the context holds now, complete when the call
+ * returns.  What a frame loop keeps as the previous pose for gbl_render_motion_deform_device.  GBL_ERR_INVALID for a NULL
+ * argument, a mesh out of range or not a triangle mesh, a range out of bounds, and the pointer refusals above. */
+gbl_status gbl_get_vertices_device(gbl_ctx* ctx, uint32_t mesh, uint32_t first, uint32_t count, float* d_positions_out);
+/* *pending = 1 while the tie order of triangle mesh `mesh` waits for its first reader (GBL_VERTICES_DEFER_ORDER), else 0.  Host
+ * only.  GBL_ERR_INVALID for a NULL argument or a mesh out of range. */
+gbl_status gbl_order_pending(const gbl_ctx* ctx, uint32_t mesh, uint32_t* pending);
 /* Self-test hook: copy records [first, first + count) of a device geometry table to host memory; *total receives the table's
  * record count.  table: 0 nodes (DevNode, 64 B), 1 tris (DevTri, 48 B), 2 tri_bounds (DevTriBound, 32 B), 3 tri_order (16 B).
  * A fifth table, 4 mesh_root (int32, 4 B per mesh of the scene: the BLAS root reference an instance of the mesh carries),
