@@ -398,6 +398,15 @@ __device__ __forceinline__ F3 eval_attenuation(const DevScene& sc, F3 o, F3 d, f
     return thr;
 }
 
+#define GBL_BOUNCE_NEW (-2)   // PathState::bounce of a path taken in this iteration, before its camera ray is made (PRIM kernels)
+
+// hit_Le (shade.h) for a caller that has loaded the hit instance's area_light already (`al`; < 0: none)
+__device__ __forceinline__ F3 area_Le(const DevScene& sc, int al, F3 n, F3 out_dir) {
+    if (al < 0) return f3(0, 0, 0);
+    const DevLight& l = sc.lights[al];
+    return dot(n, out_dir) > 0.0f ? f3(l.color[0], l.color[1], l.color[2]) : f3(0, 0, 0);
+}
+
 // ---------------------------------------------------------------------------
 // Path state carried by a lane between iterations of the persistent loop.
 // ---------------------------------------------------------------------------
@@ -787,7 +796,9 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
             bool got = false;
             if constexpr (QUAD) {
                 const bool want = active && sc.num_lights != 0;
-                if (!PRIM || __ballot(want) != 0ull)
+                // (PRIM: skipped when no lane wants a ray -- the iteration that only refills lanes which ended behind the regeneration.
+                //  The hint is for the register allocator, like the one on the round's exit below.)
+                if (!PRIM || __builtin_expect(__ballot(want) != 0ull, 1))
                     got = trace_quad<false, STATS, EXT, TIES>(sc, want, ps.o, ps.d, ps.mint, INFINITY, stk, quad_slab, quad_stack, hit, cnt);
                 if (active && !want) finished = true;
                 if (STATS && want) cnt.ext += 1;
@@ -802,7 +813,8 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
             bool vis = active;
             Frag fr;
             TexFrag tf;
-            if (vis && !finished) {
+            // (PRIM: the close step is below, around the regeneration, so that the wave issues make_fragment once per iteration)
+            if (!PRIM && vis && !finished) {
                 if (got) {
                     make_fragment<EXT>(sc, hit, ps.o, ps.d, fr, &tf);
                     if (EXT && sc.materials[sc.instances[hit.inst].material].has_tex != 0u)
@@ -896,6 +908,34 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                 // pass (kernels_quad.hip primary_kernel) found for its camera ray: the new path shades its first vertex in this same
                 // iteration, so a path costs one extension query less, and a camera ray that left the scene costs a Black and nothing else
                 // (PathTracer::Li, GoblinPathtracer.cpp:58-66).  Requires lights (the host only takes this kernel with num_lights > 0).
+                //
+                // The lanes that continue and the lanes that regenerate are complementary sets, and both need the fragment of the hit
+                // they hold, so the vertex step runs in this order and the wave issues make_fragment ONCE per iteration, for all of them:
+                //   1. decide, without a fragment: whether a path ends here depends on got, bounce and max_depth alone, and of the close
+                //      step only hit_Le reads the fragment (its normal), only when the hit instance is an area light.  Every other lane
+                //      closes its bounce here -- the expressions and their order are those of the !PRIM step above -- and hands in
+                //      its Li if the path ended, so its lane is refilled in this same iteration;
+                //   2. regenerate: idle lanes take a path and the hit the primary pass recorded for it;
+                //   3. one make_fragment for every lane that holds a hit and has not ended: the continuing lanes, the regenerated ones
+                //      (Li = 0 + Le, bounce 0) and the lanes deferred from 1., whose hit instance is an area light and which close
+                //      their bounce now, with the normal.  A deferred lane whose path ends goes out through "path end" below and is
+                //      refilled by the next iteration's round (li is indexed by out_index and the sampler is counter-based: which
+                //      iteration refills a lane changes no sample); that iteration's query is skipped when no lane wants one, so
+                //      the wave still leaves exactly when no lane holds a path after a round of regeneration.
+                static_assert(!PRIM || (QUAD && !EXT && !STATS && !REPLAY), "the primary pass feeds the lean quad kernels of the native sampler");
+                int hit_al = -1;   // the hit instance's area light, loaded once
+                const bool open = vis && !finished;   // (a tied camera ray, bounce < 0, has no bounce to close)
+                if (open && got) hit_al = sc.instances[hit.inst].area_light;
+                const bool closes = open && ps.bounce >= 0 && hit_al < 0;
+                if (closes) {
+                    // close the previous bounce; no MIS term: instances[hit].area_light == ps.light holds for no such hit
+                    F3 add = div(ps.throughput * ps.Ld, ps.pick_pdf);
+                    ps.Li = f3(ps.Li.x + add.x, ps.Li.y + add.y, ps.Li.z + add.z);
+                    F3 scale = div(ps.f * ps.cosw, ps.bsdf_pdf);
+                    ps.throughput = ps.throughput * scale;
+                    ps.bounce += 1;
+                }
+                if (open && (!got || (closes && ps.bounce >= ra.max_depth - 1))) finished = true;
                 if (vis && finished) {
                     reinterpret_cast<float4*>(ra.li_defer)[out_index] = make_float4(ps.Li.x, ps.Li.y, ps.Li.z, 1.0f);
                     active = false;
@@ -904,7 +944,13 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                 }
                 for (;;) {
                     const bool idle = !active && !exhausted;
-                    if (__ballot(idle) == 0ull) break;
+                    // (The hint on the lean kernel's exit is for the register allocator: it weighs a spilled scalar's reloads by how often
+                    //  it expects a block to run, and with the rounds marked as the cold side it keeps them out of the four traversal
+                    //  loops -- 0 v_readlane in each, against 9 to 11 without the hint and 3 before the reorder -- and in the rounds,
+                    //  where they cost an instruction per round, not per traversal step.  Under EXACT the same hint spills six vector
+                    //  registers, so that kernel goes without it.  tests/test_one_fragment_cpu.py pins both.)
+                    const bool none_idle = __ballot(idle) == 0ull;
+                    if (EXACT ? none_idle : __builtin_expect(none_idle, 1)) break;
                     if constexpr (WAVE) {
                         fetched = wave_take<true>(ra, n_items, idle, it, unit_pos, exhausted);
                         if (fetched < 0) continue;   // not idle; or beyond the unit's end: the next round's unit
@@ -920,8 +966,7 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                     src.k = static_cast<uint32_t>(it.k0 + fetched % ra.chunk_spp);
                     const int px = it.px0 + pix % it.tw, py = it.py0 + pix / it.tw;
                     out_index = static_cast<uint32_t>((py - ra.window[2]) * sub_w + (px - ra.window[0])) * ra.spp + src.k;
-                    hit.inst = ra.prim_inst[out_index];
-                    if (hit.inst == GBL_PRIM_MISS) {   // (its Black is in li already: primary_kernel)
+                    if (ra.prim_inst[out_index] == GBL_PRIM_MISS) {   // (its Black is in li already: primary_kernel)
                         paths_done += 1;
                         continue;
                     }
@@ -936,26 +981,51 @@ __global__ __launch_bounds__(GBL_BLOCK, EXT ? GBL_EXT_WAVES : GBL_PT_WAVES) void
                     ps.punch = false;
                     ps.first = true;
                     ps.path = fetched;
+                    ps.Li = f3(0.0f, 0.0f, 0.0f);
+                    ps.bounce = GBL_BOUNCE_NEW;
                     active = true;
-                    if (hit.inst == GBL_PRIM_TIED) {
-                        // the packet met two triangles at exactly this ray's closest distance: which of them a ray on its own keeps
-                        // depends on its own visiting order, so it is traced here like any other ray (next iteration's query)
-                        ps.Li = f3(0.0f, 0.0f, 0.0f);
-                        ps.bounce = -1;
-                        continue;
-                    }
-                    const float4 h = reinterpret_cast<const float4*>(ra.prim_hit)[out_index];
-                    hit.t = h.x;
-                    hit.b1 = h.y;
-                    hit.b2 = h.z;
-                    hit.tri = __float_as_uint(h.w);
-                    make_fragment<EXT>(sc, hit, ps.o, ps.d, fr, &tf);
-                    const F3 le = hit_Le(sc, hit.inst, fr.n, -ps.d);
-                    ps.Li = f3(0.0f + le.x, 0.0f + le.y, 0.0f + le.z);
-                    ps.bounce = 0;
-                    finished = ra.max_depth <= 1;
                 }
                 if (__ballot(active) == 0ull) break;
+                if (active && ps.bounce == GBL_BOUNCE_NEW) {
+                    // the hit the pass recorded for the paths just taken; its instance is read again here, once, instead of being
+                    // carried through the rounds above
+                    ps.bounce = -1;   // (3. takes the path to its first vertex)
+                    hit.inst = ra.prim_inst[out_index];
+                    // GBL_PRIM_TIED: the packet met two triangles at exactly this ray's closest distance: which of them a ray on its own
+                    // keeps depends on its own visiting order, so it is traced here like any other ray (next iteration's query)
+                    if (hit.inst != GBL_PRIM_TIED) {
+                        const float4 h = reinterpret_cast<const float4*>(ra.prim_hit)[out_index];
+                        hit.t = h.x;
+                        hit.b1 = h.y;
+                        hit.b2 = h.z;
+                        hit.tri = __float_as_uint(h.w);
+                        hit_al = sc.instances[hit.inst].area_light;
+                    }
+                }
+                // every lane that still holds a path holds a hit as well (a path without one has ended above), but for the tied camera
+                // rays just fetched; of those, the lanes that closed their bounce in 1. have no area light at their hit
+                if (active && hit.inst >= 0) {
+                    make_fragment<EXT>(sc, hit, ps.o, ps.d, fr, &tf);
+                    if (ps.bounce < 0 || hit_al >= 0) {
+                        const F3 le = area_Le(sc, hit_al, fr.n, -ps.d);
+                        if (ps.bounce < 0) {   // a path's first vertex: Li = 0 + Le
+                            ps.Li = f3(ps.Li.x + le.x, ps.Li.y + le.y, ps.Li.z + le.z);
+                            ps.bounce = 0;
+                        } else {
+                            // close the previous bounce: MIS term for the sampled direction, then Li and throughput
+                            if (hit_al == ps.light && !is_black(le)) {
+                                F3 term = div(ps.f * le * ps.cosw * ps.fw, ps.bsdf_pdf);
+                                ps.Ld = f3(ps.Ld.x + term.x, ps.Ld.y + term.y, ps.Ld.z + term.z);
+                            }
+                            F3 add = div(ps.throughput * ps.Ld, ps.pick_pdf);
+                            ps.Li = f3(ps.Li.x + add.x, ps.Li.y + add.y, ps.Li.z + add.z);
+                            F3 scale = div(ps.f * ps.cosw, ps.bsdf_pdf);
+                            ps.throughput = ps.throughput * scale;
+                            ps.bounce += 1;
+                        }
+                        if (ps.bounce >= ra.max_depth - 1) finished = true;
+                    }
+                }
                 vis = active && ps.bounce >= 0;   // (a tied camera ray has nothing to shade yet)
             }
 
