@@ -183,6 +183,11 @@ class gbl_motion_mesh(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("reserved", C.c_uint32), ("positions", C.c_void_p)]
 
 
+class gbl_tree_stats(C.Structure):
+    _fields_ = [("nodes", C.c_uint32), ("levels", C.c_uint32), ("leaves", C.c_uint32), ("reserved", C.c_uint32),
+                ("root_area", C.c_double), ("node_area", C.c_double), ("tri_area", C.c_double)]
+
+
 class gbl_info(C.Structure):
     _fields_ = [("xres", C.c_int32), ("yres", C.c_int32), ("window", C.c_int32 * 4), ("blas_nodes", C.c_uint64),
                 ("tlas_nodes", C.c_uint64), ("triangles", C.c_uint64), ("instances", C.c_uint64),
@@ -196,7 +201,7 @@ HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "
                 "gbl_host_bloom", "gbl_host_tone_map", "gbl_host_write_ppm", "gbl_host_write_ppm8", "gbl_host_write_exr", "gbl_host_write_image",
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_rebuild_mesh", "gbl_mesh_tree_stats", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
                "gbl_aov_resolve_depth", "gbl_film_variance", "gbl_film_denoise", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
@@ -298,6 +303,8 @@ def hip_lib():
         lib.gbl_update_vertices_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         lib.gbl_get_vertices_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.gbl_order_pending.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.gbl_rebuild_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.gbl_mesh_tree_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(gbl_tree_stats)]
         lib.gbl_render_motion_deform_device.argtypes = [C.c_void_p, C.POINTER(gbl_motion_params), C.POINTER(gbl_motion_mesh), C.c_uint32, C.c_void_p]
         lib.gbl_selftest_geometry.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
         lib.gbl_update_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]

@@ -199,6 +199,8 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
             if (desc->meshes[m].shape == GBL_SHAPE_MESH) packed.mesh_root[m] = mesh_root[m];
         packed.blas_max_depth = max_depth;
         packed.blas_nodes = static_cast<uint64_t>(node_base) - packed.nodes.size();
+        if (ctx->lbvh_scratch.p) (void)hipFree(ctx->lbvh_scratch.p);   // a context that never rebuilds a mesh holds no builder scratch
+        ctx->lbvh_scratch = gbl_buf();
         {   // device-built trees: the per-level bound of each mesh's BLAS under the exact TLAS sum
             const std::vector<DevNode> tl(packed.nodes.begin() + packed.tlas_base, packed.nodes.begin() + packed.tlas_base + static_cast<std::ptrdiff_t>(packed.tlas_nodes));
             packed.stack_entries = scene_stack_entries(tl, packed.tlas_base, packed.tlas_root, packed.instances, packed.mesh_stack_need);
@@ -293,6 +295,8 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
     for (uint32_t i = 0; i < desc->num_lights; ++i)
         if (desc->lights[i].type == GBL_LIGHT_AREA && desc->lights[i].mesh < desc->num_meshes) ctx->mesh_emits[desc->lights[i].mesh] = 1;
     ctx->refit.assign(desc->num_meshes, gbl_ctx::MeshRefit());
+    ctx->rebuild_slot.assign(desc->num_meshes, -1);
+    ctx->rebuild_idx.assign(desc->num_meshes, nullptr);
     if (getenv("GBL_PROBE"))
         fprintf(stderr, "probe: traversal stack entries %d (per-level bound %d: TLAS depth %d, BLAS depth %d)\n", packed.stack_entries,
                 3 * (packed.tlas_depth + packed.blas_max_depth) + 2, packed.tlas_depth, packed.blas_max_depth);
@@ -367,7 +371,8 @@ void gbl_destroy(gbl_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     for (void* p : ctx->allocations) (void)hipFree(p);
     for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->aov, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
-                       &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter, &ctx->denoise, &ctx->temporal, &ctx->motion, &ctx->motion_deform, &ctx->vertex_words, &ctx->pose_words})
+                       &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter, &ctx->denoise, &ctx->temporal, &ctx->motion, &ctx->motion_deform, &ctx->vertex_words, &ctx->pose_words,
+                       &ctx->lbvh_scratch, &ctx->tree_stats})
         if (b->p) (void)hipFree(b->p);
     if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
     if (ctx->wf_ev_shade) (void)hipEventDestroy(ctx->wf_ev_shade);

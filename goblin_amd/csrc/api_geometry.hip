@@ -2,7 +2,8 @@
 // mesh's BLAS on the device in place (kernels/refit.h over the plan of scene_refit.h); gbl_get_vertices and the
 // geometry tables' read-back go with it.  gbl_update_vertices_device and gbl_get_vertices_device are the same two over device
 // memory (kernels/vertices.h): the host copy of the positions turns into a mirror refreshed on demand, and the tie order may
-// wait for its first reader (make_pending_orders, gbl_host.h).
+// wait for its first reader (make_pending_orders, gbl_host.h).  gbl_rebuild_mesh builds a deformed mesh's tree again with the
+// device builder (kernels/lbvh.h), and gbl_mesh_tree_stats (kernels/treestats.h) tells a caller when that pays.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -77,8 +78,43 @@ gbl_status ensure_plan(gbl_ctx* ctx, uint32_t mesh) {
         if (st != GBL_OK) return st;
         HIP_TRY(ctx, hipMemcpy(mr.plan, plan.records.data(), plan.records.size() * sizeof(RefitRecord), hipMemcpyHostToDevice));
     }
+    mr.leaves = plan.records.empty() ? 1u : 0u;   // (a root that is itself a leaf)
+    for (const RefitRecord& rec : plan.records)
+        for (int c = 0; c < 4; ++c) mr.leaves += ctx->h_nodes[rec.node].child[c] < 0 ? 1u : 0u;
     mr.level_first.swap(plan.level_first);
     mr.built = true;
+    return GBL_OK;
+}
+
+// Forget the mesh's refit plan (its tree is about to be replaced): the next edit, or gbl_mesh_tree_stats, makes it again
+void drop_plan(gbl_ctx* ctx, uint32_t mesh) {
+    gbl_ctx::MeshRefit& mr = ctx->refit[mesh];
+    for (void* p : {static_cast<void*>(mr.plan), static_cast<void*>(mr.node_box)}) {
+        if (!p) continue;
+        ctx->allocations.erase(std::remove(ctx->allocations.begin(), ctx->allocations.end(), p), ctx->allocations.end());
+        (void)hipFree(p);
+    }
+    mr = gbl_ctx::MeshRefit();
+}
+
+// The node array regrown by `extra` zeroed records behind the ones it holds: every index stays valid, tlas_base included.  The
+// caller has synchronised the device; the old array is freed once the copy is done.
+gbl_status grow_nodes(gbl_ctx* ctx, uint32_t extra, int32_t* first_new) {
+    const uint64_t old_n = ctx->num_nodes, new_n = old_n + extra;
+    if (new_n >= static_cast<uint64_t>(GBL_REF_NONE)) return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_rebuild_mesh: the node array would outgrow a child reference");
+    void* grown = nullptr;
+    const gbl_status st = device_alloc(ctx, new_n * sizeof(DevNode), "nodes", &grown);
+    if (st != GBL_OK) return st;
+    DevNode* const old = const_cast<DevNode*>(ctx->scene.nodes);
+    if (old_n > 0) HIP_TRY(ctx, hipMemcpy(grown, old, old_n * sizeof(DevNode), hipMemcpyDeviceToDevice));
+    HIP_TRY(ctx, hipMemset(static_cast<DevNode*>(grown) + old_n, 0, extra * sizeof(DevNode)));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->allocations.erase(std::remove(ctx->allocations.begin(), ctx->allocations.end(), static_cast<void*>(old)), ctx->allocations.end());
+    (void)hipFree(old);
+    ctx->scene.nodes = static_cast<const DevNode*>(grown);
+    ctx->num_nodes = new_n;
+    ctx->info.scene_bytes += static_cast<uint64_t>(extra) * sizeof(DevNode);
+    *first_new = static_cast<int32_t>(old_n);
     return GBL_OK;
 }
 
@@ -251,6 +287,107 @@ gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t
     return GBL_OK;
 }
 
+// What gbl_rebuild_mesh and gbl_mesh_tree_stats refuse alike: the mesh must be a triangle mesh of the scene
+gbl_status check_tree_mesh(gbl_ctx* ctx, uint32_t mesh, const char* who) {
+    if (mesh >= ctx->h_meshes.size()) return fail(ctx, GBL_ERR_INVALID, std::string(who) + ": mesh " + std::to_string(mesh) + " is out of range");
+    if (ctx->h_meshes[mesh].shape != GBL_SHAPE_MESH)
+        return fail(ctx, GBL_ERR_INVALID, std::string(who) + ": mesh " + std::to_string(mesh) + " is a sphere or a disk: it has no tree");
+    if (static_cast<uint64_t>(ctx->mesh_tri_first[mesh]) + ctx->h_meshes[mesh].tri_count > ctx->info.triangles)
+        return fail(ctx, GBL_ERR_INTERNAL, std::string(who) + ": the mesh's triangles lie outside the triangle table");
+    return GBL_OK;
+}
+
+// The mesh's BLAS built again by the device builder (kernels/lbvh.h through gbl_build_blas_device) over the positions the
+// device holds: triangles in the new Morton order in the mesh's own range, their bounds by refit_tris' rule, the tree in the
+// mesh's tail slot of the node array.  Neither tri_order nor the pending state nor the mirror is read or written.
+gbl_status gbl_rebuild_mesh_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
+    if (!ctx) return GBL_ERR_INVALID;
+    gbl_status st = check_tree_mesh(ctx, mesh, "gbl_rebuild_mesh");
+    if (st != GBL_OK) return st;
+    if (flags != 0) return fail(ctx, GBL_ERR_INVALID, "gbl_rebuild_mesh: flags is reserved and must be 0");
+    if (ctx->mesh_emits[mesh])
+        return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_rebuild_mesh: mesh " + std::to_string(mesh) + " is the geometry of an area light, whose emitting "
+                                              "triangles are listed by their place in the triangle table; re-create the context instead");
+    const gbl_mesh& gm = ctx->h_meshes[mesh];
+    const uint32_t n = gm.tri_count, tri_first = ctx->mesh_tri_first[mesh];
+    if (n == 0) return GBL_OK;
+    const auto now = [] { return std::chrono::steady_clock::now(); };
+    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables
+    // first rebuild of the mesh: its index slice goes up (a host-built context has none on the device), and a mesh with a tree
+    // gets tri_count records behind the node array -- gbl_create's own bound for a device-built mesh -- for good
+    if (!ctx->rebuild_idx[mesh]) {
+        void* p = nullptr;
+        if ((st = device_alloc(ctx, 3 * static_cast<size_t>(n) * sizeof(uint32_t), "rebuild indices", &p)) != GBL_OK) return st;
+        HIP_TRY(ctx, hipMemcpy(p, ctx->h_indices.data() + 3 * static_cast<size_t>(gm.tri_offset), 3 * static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        ctx->rebuild_idx[mesh] = static_cast<uint32_t*>(p);
+    }
+    if (n > GBL_MAX_LEAF_TRIS && ctx->rebuild_slot[mesh] < 0) {
+        if ((st = grow_nodes(ctx, n, &ctx->rebuild_slot[mesh])) != GBL_OK) return st;
+        ctx->h_nodes.clear();
+    }
+    const auto t1 = now();
+    DevScene& sc = ctx->scene;
+    int32_t root = 0;
+    uint32_t used = 0;
+    int depth = 0;
+    st = gbl_build_blas_device(ctx, sc.positions + 3 * static_cast<size_t>(gm.vertex_offset), ctx->rebuild_idx[mesh], n, &ctx->mesh_lo[3 * mesh], &ctx->mesh_hi[3 * mesh],
+                               const_cast<DevNode*>(sc.nodes), std::max(ctx->rebuild_slot[mesh], 0), const_cast<DevTri*>(sc.tris), tri_first, gm.tri_offset,
+                               (gm.has_normal ? 1u : 0u) | (gm.has_uv ? 2u : 0u), &root, &used, &depth);
+    if (st != GBL_OK) return st;
+    if (used > n) return fail(ctx, GBL_ERR_INTERNAL, "gbl_rebuild_mesh: the tree outgrew the mesh's node records");
+    const auto t2 = now();
+    gbl_launch_refit_tris(const_cast<DevTri*>(sc.tris), const_cast<DevTriBound*>(sc.tri_bounds), sc.tri_shade, sc.positions,
+                          static_cast<uint32_t>(ctx->h_positions.size() / 3), tri_first, n, 0);
+    HIP_TRY(ctx, hipGetLastError());
+    drop_plan(ctx, mesh);     // the next edit makes its plan over the new tree ...
+    ctx->h_nodes.clear();     // ... from a new download of the node array
+    ctx->mesh_root[mesh] = root;
+    ctx->mesh_stack_need[mesh] = 3 * depth;
+    ctx->blas_depth = std::max(ctx->blas_depth, depth);
+    ctx->info.blas_depth = ctx->blas_depth;   // (a bound from here on: the deepest tree any mesh of the context has had)
+    std::vector<gbl_instance> instances = ctx->h_instances;
+    st = rebuild_tlas(ctx, instances, "gbl_rebuild_mesh");   // (synchronises before its uploads, recomputes stack_entries, and clears the AUTO pilot)
+    if (st != GBL_OK) return st;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (getenv("GBL_PROBE"))
+        fprintf(stderr, "probe: gbl_rebuild_mesh mesh %u (%u triangles -> %u nodes, %d levels, slot %d): synchronise, indices and slot %.3f ms, build kernels "
+                        "(one read-back per level) %.3f ms, triangle bounds and TLAS %.3f ms\n", mesh, n, used, depth, ctx->rebuild_slot[mesh], ms(t0, t1), ms(t1, t2),
+                ms(t2, now()));
+    return GBL_OK;
+}
+
+gbl_status gbl_mesh_tree_stats_impl(gbl_ctx* ctx, uint32_t mesh, gbl_tree_stats* out) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (!out) return fail(ctx, GBL_ERR_INVALID, "gbl_mesh_tree_stats: out is NULL");
+    gbl_status st = check_tree_mesh(ctx, mesh, "gbl_mesh_tree_stats");
+    if (st != GBL_OK) return st;
+    memset(out, 0, sizeof(*out));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // (an edit's launches are done: the boxes read are the ones the next render tests)
+    if ((st = ensure_plan(ctx, mesh)) != GBL_OK) return st;
+    const gbl_ctx::MeshRefit& mr = ctx->refit[mesh];
+    const uint32_t records = mr.level_first.empty() ? 0u : mr.level_first.back();
+    out->nodes = records;
+    out->levels = mr.level_first.empty() ? 0u : static_cast<uint32_t>(mr.level_first.size() - 1);
+    out->leaves = mr.leaves;
+    if (records == 0) return GBL_OK;   // the root is a leaf
+    const uint32_t blocks = (records + GBL_BLOCK - 1) / GBL_BLOCK;
+    if ((st = grow(ctx, ctx->tree_stats, (3 + 2 * static_cast<uint64_t>(blocks)) * sizeof(double), "tree statistics")) != GBL_OK) return st;
+    double* sums = static_cast<double*>(ctx->tree_stats.p);
+    HIP_TRY(ctx, hipMemsetAsync(sums, 0, 3 * sizeof(double), 0));
+    gbl_launch_tree_stats(ctx->scene.nodes, ctx->num_nodes, mr.plan, records, sums, sums + 3, 0);
+    HIP_TRY(ctx, hipGetLastError());
+    double h[3] = {0.0, 0.0, 0.0};
+    HIP_TRY(ctx, hipMemcpy(h, sums, sizeof(h), hipMemcpyDeviceToHost));
+    out->root_area = h[0];
+    out->node_area = h[1];
+    out->tri_area = h[2];
+    return GBL_OK;
+}
+
 gbl_status gbl_get_vertices_impl(const gbl_ctx* cctx, uint32_t mesh, uint32_t first, uint32_t count, float* positions_out) {
     if (!cctx || !positions_out || mesh >= cctx->h_meshes.size()) return GBL_ERR_INVALID;
     gbl_ctx* ctx = const_cast<gbl_ctx*>(cctx);   // (the mirror is a cache of the device's positions: refreshing it changes nothing a caller can see)
@@ -349,6 +486,14 @@ gbl_status gbl_get_vertices_device(gbl_ctx* ctx, uint32_t mesh, uint32_t first, 
 
 gbl_status gbl_order_pending(const gbl_ctx* ctx, uint32_t mesh, uint32_t* pending) {
     return gbl_guard([&] { return gbl_order_pending_impl(ctx, mesh, pending); }, [&](const std::string&) {});
+}
+
+gbl_status gbl_rebuild_mesh(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
+    return gbl_guard([&] { return gbl_rebuild_mesh_impl(ctx, mesh, flags); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
+
+gbl_status gbl_mesh_tree_stats(gbl_ctx* ctx, uint32_t mesh, gbl_tree_stats* out) {
+    return gbl_guard([&] { return gbl_mesh_tree_stats_impl(ctx, mesh, out); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
 }
 
 gbl_status gbl_selftest_geometry(gbl_ctx* ctx, int table, uint64_t first, uint64_t count, void* out, uint64_t* total) {

@@ -97,6 +97,7 @@ struct gbl_ctx {
     struct MeshRefit {
         bool built = false;
         std::vector<uint32_t> level_first;   // scene_refit.h RefitPlan::level_first
+        uint32_t leaves = 0;                 // leaf slots of the plan's nodes; 1 when the root itself is a leaf (gbl_mesh_tree_stats)
         RefitRecord* plan = nullptr;         // device: the plan's records ...
         RefitBox* node_box = nullptr;        // ... and a box per record
     };
@@ -107,6 +108,11 @@ struct gbl_ctx {
     uint32_t orders_pending = 0;                // ... how many are set
     gbl_buf vertex_words;     // six 64-bit keys and the check word (64 bytes, all ones before a call's launches), then the bound's six floats
     gbl_buf pose_words;       // gbl_render_motion_deform_device: per listed mesh a check word, a differs flag and its PoseList record
+    // what gbl_rebuild_mesh and gbl_mesh_tree_stats keep (api_geometry.hip)
+    gbl_buf lbvh_scratch;                    // gbl_build_blas_device's scratch, one allocation carved up per build (kernels_aux.hip)
+    std::vector<int32_t> rebuild_slot;       // per mesh: the first of the tri_count node records its rebuilt trees are written to; -1: none yet
+    std::vector<uint32_t*> rebuild_idx;      // per mesh: its slice of h_indices on the device, uploaded at its first rebuild
+    gbl_buf tree_stats;                      // three sums (root, node and triangle area), then two partial sums per workgroup (kernels/treestats.h)
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
@@ -194,6 +200,10 @@ void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade*
                            uint32_t count, hipStream_t stream);
 void gbl_launch_refit_level(DevNode* nodes, const DevTriBound* bounds, const RefitRecord* plan, RefitBox* node_box, uint32_t begin, uint32_t end,
                             hipStream_t stream);
+// ... and of gbl_mesh_tree_stats (kernels/treestats.h): sums[0..3) = {root_area, node_area, tri_area}, partial holds two
+// doubles per workgroup of GBL_BLOCK plan records
+void gbl_launch_tree_stats(const DevNode* nodes, uint64_t num_nodes, const RefitRecord* plan, uint32_t num_records, double* sums, double* partial,
+                           hipStream_t stream);
 // kernels_vertices.hip: the passes of the device-pointer vertex entries (kernels/vertices.h).  first_bad, keys and differs are
 // set by the caller before the launch (all ones, all ones, zero); `list` holds num_listed PoseList records on the device
 void gbl_launch_vertices_check(const float* positions, const float* normals, uint32_t n, uint32_t* first_bad, hipStream_t stream);
@@ -202,4 +212,4 @@ void gbl_launch_pose_differs(const PoseList* list, uint32_t num_listed, uint32_t
                              hipStream_t stream);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
-                                 int32_t* root_out, uint32_t* nodes_out, int* depth_out);
+                                 int32_t* root_out, uint32_t* nodes_out, int* depth_out);   // (its scratch is ctx->lbvh_scratch, grown on demand)

@@ -77,40 +77,45 @@ void gbl_launch_quantize(const float* rgb, uint8_t* rgb8, int n, hipStream_t str
 // Device BLAS build (kernels/lbvh.h).  One mesh at a time: nodes are written at node_base (absolute child
 // references), DevTri records at tri_base in Morton order.  Returns the mesh's root reference.
 // ---------------------------------------------------------------------------
-namespace {
-struct LbvhScratch {
-    std::vector<void*> ptrs;
-    ~LbvhScratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    bool alloc(T** out, size_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return false;
-        ptrs.push_back(p);
-        *out = static_cast<T*>(p);
-        return true;
-    }
-};
-}  // namespace
-
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                              DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                              int32_t* root_out, uint32_t* nodes_out, int* depth_out) {
-    LbvhScratch sc;
-    unsigned long long *keys = nullptr, *keys_sorted = nullptr;
-    LbvhBox* tri_box = nullptr;
+    // the scratch: one buffer of the context, grown on demand and carved up here (a rebuild per pose allocates nothing)
+    const size_t ni = n > 1 ? n - 1 : 1;
+    size_t temp_bytes = 0;
+    HIP_TRY(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, static_cast<unsigned long long*>(nullptr), static_cast<unsigned long long*>(nullptr),
+                                                   static_cast<int>(n), 0, 62));
+    size_t scratch_bytes = 0;
+    const auto take = [&](size_t count, size_t size) {
+        const size_t at = scratch_bytes;
+        scratch_bytes += (std::max<size_t>(1, count) * size + 255) & ~static_cast<size_t>(255);
+        return at;
+    };
+    const size_t o_keys = take(n, sizeof(unsigned long long)), o_sorted = take(n, sizeof(unsigned long long)), o_tri_box = take(n, sizeof(LbvhBox));
+    const size_t o_left = take(ni, sizeof(int32_t)), o_right = take(ni, sizeof(int32_t)), o_parent = take(2 * static_cast<size_t>(n), sizeof(int32_t));
+    const size_t o_first = take(ni, sizeof(uint32_t)), o_last = take(ni, sizeof(uint32_t)), o_box = take(ni, sizeof(LbvhBox)), o_leaf_box = take(n, sizeof(LbvhBox));
+    const size_t o_visits = take(ni, sizeof(uint32_t)), o_fa = take(ni, sizeof(LbvhFrontier)), o_fb = take(ni, sizeof(LbvhFrontier));
+    const size_t o_counters = take(2, sizeof(uint32_t)), o_temp = take(temp_bytes, 1);
+    const gbl_status grown = grow(ctx, ctx->lbvh_scratch, scratch_bytes, "device BVH build scratch");
+    if (grown != GBL_OK) return grown;
+    unsigned char* const base = static_cast<unsigned char*>(ctx->lbvh_scratch.p);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + o_keys);
+    unsigned long long* keys_sorted = reinterpret_cast<unsigned long long*>(base + o_sorted);
+    LbvhBox* tri_box = reinterpret_cast<LbvhBox*>(base + o_tri_box);
     LbvhTree t;
     memset(&t, 0, sizeof(t));
-    LbvhFrontier *fa = nullptr, *fb = nullptr;
-    uint32_t* counters = nullptr;   // [0] next frontier size, [1] nodes emitted
-    const size_t ni = n > 1 ? n - 1 : 1;
-    if (!sc.alloc(&keys, n) || !sc.alloc(&keys_sorted, n) || !sc.alloc(&tri_box, n) || !sc.alloc(&t.left, ni) || !sc.alloc(&t.right, ni) ||
-        !sc.alloc(&t.parent, 2 * static_cast<size_t>(n)) || !sc.alloc(&t.first, ni) || !sc.alloc(&t.last, ni) || !sc.alloc(&t.box, ni) ||
-        !sc.alloc(&t.leaf_box, n) || !sc.alloc(&t.visits, ni) || !sc.alloc(&fa, ni) || !sc.alloc(&fb, ni) || !sc.alloc(&counters, 2)) {
-        ctx->error = "hipMalloc(device BVH build scratch) failed";
-        return GBL_ERR_OOM;
-    }
+    t.left = reinterpret_cast<int32_t*>(base + o_left);
+    t.right = reinterpret_cast<int32_t*>(base + o_right);
+    t.parent = reinterpret_cast<int32_t*>(base + o_parent);
+    t.first = reinterpret_cast<uint32_t*>(base + o_first);
+    t.last = reinterpret_cast<uint32_t*>(base + o_last);
+    t.box = reinterpret_cast<LbvhBox*>(base + o_box);
+    t.leaf_box = reinterpret_cast<LbvhBox*>(base + o_leaf_box);
+    t.visits = reinterpret_cast<uint32_t*>(base + o_visits);
+    LbvhFrontier* fa = reinterpret_cast<LbvhFrontier*>(base + o_fa);
+    LbvhFrontier* fb = reinterpret_cast<LbvhFrontier*>(base + o_fb);
+    uint32_t* counters = reinterpret_cast<uint32_t*>(base + o_counters);   // [0] next frontier size, [1] nodes emitted
+    unsigned char* temp = base + o_temp;
     LbvhBox mesh;
     for (int a = 0; a < 3; ++a) {
         mesh.lo[a] = lo[a];
@@ -118,13 +123,6 @@ gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_
     }
     const dim3 block(256), grid((n + 255) / 256);
     hipLaunchKernelGGL(lbvh_keys, grid, block, 0, 0, d_pos, d_idx, n, mesh, keys, tri_box);
-    size_t temp_bytes = 0;
-    HIP_TRY(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, temp_bytes, keys, keys_sorted, static_cast<int>(n), 0, 62));
-    unsigned char* temp = nullptr;
-    if (!sc.alloc(&temp, temp_bytes)) {
-        ctx->error = "hipMalloc(radix sort scratch) failed";
-        return GBL_ERR_OOM;
-    }
     HIP_TRY(ctx, hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, keys, keys_sorted, static_cast<int>(n), 0, 62));
     hipLaunchKernelGGL(lbvh_tris, grid, block, 0, 0, d_pos, d_idx, keys_sorted, n, shade_base, tri_flags, d_tris + tri_base);
     *nodes_out = 0;

@@ -177,6 +177,30 @@ class HipPathTracer:
             raise _abi.GoblinError(st, "gbl_order_pending")
         return int(pending.value)
 
+    def rebuild_mesh(self, mesh):
+        """Build the BLAS of triangle mesh ``mesh`` again on the device, in place, over the positions the context holds now
+        (gbl_rebuild_mesh): afterwards the mesh's triangles, bounds and tree are what a ``bvh="device"`` tracer of the deformed
+        scene holds, whichever builder made this one.  For a pose that is rendered many times after a large deformation
+        (``tree_stats`` tells when); a deferred tie order stays deferred."""
+        st = self.lib.gbl_rebuild_mesh(self.handle, int(mesh), 0)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        self.lib.gbl_get_info(self.handle, C.byref(self.info))
+
+    def tree_stats(self, mesh):
+        """Size and expected traversal cost of the BLAS of triangle mesh ``mesh`` as it is now (gbl_mesh_tree_stats): a dict of
+        nodes, levels, leaves; root_area, node_area, tri_area (sums over the quantised child boxes); and the two ratios
+        node_cost = 1 + node_area / root_area -- the expected number of nodes a ray that enters the root visits -- and
+        tri_cost = tri_area / root_area, the expected number of triangles it tests (both 0.0 when root_area is 0)."""
+        ts = _abi.gbl_tree_stats()
+        st = self.lib.gbl_mesh_tree_stats(self.handle, int(mesh), C.byref(ts))
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        out = {name: getattr(ts, name) for name in ("nodes", "levels", "leaves", "root_area", "node_area", "tri_area")}
+        out["node_cost"] = 1.0 + ts.node_area / ts.root_area if ts.root_area > 0 else 0.0
+        out["tri_cost"] = ts.tri_area / ts.root_area if ts.root_area > 0 else 0.0
+        return out
+
     _GEOMETRY = (np.dtype([("o", "<f4", 3), ("scale", "<f4", 3), ("qlo", "<u4", 3), ("qhi", "<u4", 3), ("child", "<i4", 4)]),
                  np.dtype([("p0", "<f4", 3), ("shade", "<u4"), ("e1", "<f4", 3), ("flags", "<u4"), ("e2", "<f4", 3), ("pad1", "<f4")]),
                  np.dtype([("lo", "<f4", 3), ("hi", "<f4", 3), ("pad", "<f4", 2)]),

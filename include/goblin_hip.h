@@ -735,7 +735,7 @@ gbl_status gbl_get_instances(const gbl_ctx* ctx, uint32_t first, uint32_t count,
  *    reference's visiting order (what exact ties are broken by), the mesh's object bound, the instance bounds and the TLAS.
  *  - After the call every table the kernels read is what it would be for the edited positions over the same tree, and a render
  *    equals, bit for bit, that of a context created from the edited scene.  A tree refitted after a large deformation is valid
- *    but slower to trace than a new one: re-create the context to rebuild it.
+ *    but slower to trace than a new one: gbl_mesh_tree_stats measures it and gbl_rebuild_mesh builds it again in place.
  *  - The call synchronises the device, as gbl_update_instances does, and GBL_SCHEDULE_AUTO measures its rays per path again.
  *  - normals == NULL: the mesh's vertex normals stay as they were.  The caller owns that choice.
  *  - gbl_render_motion's planes follow cameras and instances only; gbl_render_motion_deform also takes the positions a mesh had
@@ -787,6 +787,48 @@ gbl_status gbl_get_vertices_device(gbl_ctx* ctx, uint32_t mesh, uint32_t first, 
 /* *pending = 1 while the tie order of triangle mesh `mesh` waits for its first reader (GBL_VERTICES_DEFER_ORDER), else 0.  Host
  * only.  GBL_ERR_INVALID for a NULL argument or a mesh out of range. */
 gbl_status gbl_order_pending(const gbl_ctx* ctx, uint32_t mesh, uint32_t* pending);
+
+/* Rebuild the BLAS of triangle mesh `mesh` on the device, in place, over the positions the context holds now (gbl_create's, or
+ * the last gbl_update_vertices* edit's): what a frame loop calls once a refitted tree has grown slow (gbl_mesh_tree_stats),
+ * instead of re-creating the context and losing its pools, pilot, planes and history.
+ *  - Afterwards every table the kernels read is what gbl_create_ex(..., GBL_CREATE_DEVICE_BVH) makes for this mesh over the same
+ *    positions, whichever builder made the context: the mesh's triangles in the new Morton order (its range of the triangle
+ *    table does not move), their bounds, and the linear BVH's nodes.  A render equals, bit for bit, that of a device-built
+ *    context created from the deformed scene.
+ *  - The tree goes into a slot of tri_count node records appended to the node array at the mesh's first rebuild (one device
+ *    allocation and a device-to-device copy; every index stays valid) and reused by every later one; the builder's scratch is
+ *    kept and grown on demand, so a rebuild per pose allocates nothing.  The records the old tree occupied stay unreferenced.
+ *    A mesh of four triangles or fewer is one leaf and needs no slot.
+ *  - Order of the call: synchronise; the slot; the build kernels (a 64-bit radix sort, and one 8-byte read-back per level of
+ *    the tree); the triangle bounds; the TLAS on the host as in every edit; synchronise.  GBL_SCHEDULE_AUTO measures its rays
+ *    per path again, and gbl_info.blas_depth becomes the deepest tree any mesh of the context has had.
+ *  - The tie order is indexed by original triangle and is neither read nor written: a deferred order stays deferred.
+ *  - The mesh's refit plan is dropped; the next gbl_update_vertices* makes it over the new tree.
+ *  - Limit: in a host-built context the rebuilt tree's top nodes are no longer among the hot prefix the lean kernels keep in LDS.
+ * flags is reserved and must be 0.  GBL_ERR_INVALID, the context untouched: a NULL ctx, a mesh out of range or a sphere or a
+ * disk, non-zero flags.  GBL_ERR_UNSUPPORTED, the context untouched: a mesh an area light emits from (its emitting triangles
+ * are listed by their place in the triangle table, and such a mesh cannot have been edited).  Scenes with a directional or image
+ * based light are not refused: nothing those lights read changes. */
+gbl_status gbl_rebuild_mesh(gbl_ctx* ctx, uint32_t mesh, uint32_t flags);
+
+/* The size and the expected traversal cost of the BLAS of triangle mesh `mesh` as it is now.  The three counts come from the
+ * mesh's refit plan (made here if no edit has made it: one download of the node array); the three sums are taken on the device
+ * over the QUANTISED child boxes -- the boxes traversal tests: a slot's corner on axis a is o[a] + (float)q * scale[a] in float32,
+ * its area dx * dy + dy * dz + dz * dx in double.  node_area / root_area is then the expected number of interior children a
+ * ray that enters the root visits, tri_area / root_area the expected number of triangles it tests: both grow as a refitted tree
+ * degrades, and a caller rebuilds (gbl_rebuild_mesh) when they have grown too far.  No atomics: two calls return the same bits.
+ * A mesh whose root is a leaf reports nodes = levels = 0, leaves = 1 and zero sums.  Synchronises the device.
+ * GBL_ERR_INVALID for a NULL argument, a mesh out of range or a sphere or a disk. */
+typedef struct gbl_tree_stats {
+    uint32_t nodes;      /* interior (4-wide) nodes reached from the mesh's root */
+    uint32_t levels;     /* levels of them, the root's included */
+    uint32_t leaves;     /* leaf slots: groups of one to four triangles */
+    uint32_t reserved;
+    double root_area;    /* area of the union of the root's used slots */
+    double node_area;    /* sum over the used interior child slots of every node */
+    double tri_area;     /* sum over the leaf slots of triangle count * area */
+} gbl_tree_stats;
+gbl_status gbl_mesh_tree_stats(gbl_ctx* ctx, uint32_t mesh, gbl_tree_stats* out);
 /* Self-test hook: copy records [first, first + count) of a device geometry table to host memory; *total receives the table's
  * record count.  table: 0 nodes (DevNode, 64 B), 1 tris (DevTri, 48 B), 2 tri_bounds (DevTriBound, 32 B), 3 tri_order (16 B).
  * A fifth table, 4 mesh_root (int32, 4 B per mesh of the scene: the BLAS root reference an instance of the mesh carries),
