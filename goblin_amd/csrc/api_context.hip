@@ -331,9 +331,12 @@ static gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32
                          "have to move with it; re-create the context instead";
             return GBL_ERR_UNSUPPORTED;
         }
+    gbl_status st = refresh_instance_mirror(ctx);   // (a device instance edit may have left the transforms' host copy behind)
+    if (st != GBL_OK) return st;
     std::vector<gbl_instance> edited = ctx->h_instances;
     for (uint32_t i = 0; i < count; ++i) edited[first + i].to_world = to_world[i];
-    return rebuild_tlas(ctx, edited, "gbl_update_instances");
+    if ((st = rebuild_tlas(ctx, edited, "gbl_update_instances")) != GBL_OK) return st;
+    return write_instance_table(ctx, first, count);
 }
 gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
     return gbl_guard([&] { return gbl_update_instances_impl(ctx, first, count, to_world); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
@@ -372,7 +375,7 @@ void gbl_destroy(gbl_ctx* ctx) {
     for (void* p : ctx->allocations) (void)hipFree(p);
     for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->aov, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
                        &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter, &ctx->denoise, &ctx->temporal, &ctx->motion, &ctx->motion_deform, &ctx->vertex_words, &ctx->pose_words,
-                       &ctx->lbvh_scratch, &ctx->tree_stats})
+                       &ctx->lbvh_scratch, &ctx->tree_stats, &ctx->inst_stage})
         if (b->p) (void)hipFree(b->p);
     if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
     if (ctx->wf_ev_shade) (void)hipEventDestroy(ctx->wf_ev_shade);

@@ -202,6 +202,7 @@ gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first,
     if ((st = make_order(ctx, mesh)) != GBL_OK) return st;
     const auto t2 = now();
     mesh_object_bound(ctx->h_positions.data() + 3 * static_cast<size_t>(gm.vertex_offset), gm.vertex_count, &ctx->mesh_lo[3 * mesh], &ctx->mesh_hi[3 * mesh]);
+    if ((st = refresh_instance_mirror(ctx)) != GBL_OK) return st;   // (a device instance edit may have left the transforms' host copy behind)
     std::vector<gbl_instance> instances = ctx->h_instances;
     st = rebuild_tlas(ctx, instances, "gbl_update_vertices");   // (synchronises before its uploads, and clears the AUTO pilot)
     if (st != GBL_OK) return st;
@@ -277,6 +278,7 @@ gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t
     float bound[6];
     HIP_TRY(ctx, hipMemcpy(bound, words + GBL_VW_BOUND, sizeof(bound), hipMemcpyDeviceToHost));
     for (int a = 0; a < 3; ++a) ctx->mesh_lo[3 * mesh + a] = bound[a], ctx->mesh_hi[3 * mesh + a] = bound[3 + a];
+    if ((st = refresh_instance_mirror(ctx)) != GBL_OK) return st;   // (a device instance edit may have left the transforms' host copy behind)
     std::vector<gbl_instance> instances = ctx->h_instances;
     st = rebuild_tlas(ctx, instances, "gbl_update_vertices_device");   // (synchronises before its uploads, and clears the AUTO pilot)
     if (st != GBL_OK) return st;
@@ -348,6 +350,7 @@ gbl_status gbl_rebuild_mesh_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
     ctx->mesh_stack_need[mesh] = 3 * depth;
     ctx->blas_depth = std::max(ctx->blas_depth, depth);
     ctx->info.blas_depth = ctx->blas_depth;   // (a bound from here on: the deepest tree any mesh of the context has had)
+    if ((st = refresh_instance_mirror(ctx)) != GBL_OK) return st;   // (a device instance edit may have left the transforms' host copy behind)
     std::vector<gbl_instance> instances = ctx->h_instances;
     st = rebuild_tlas(ctx, instances, "gbl_rebuild_mesh");   // (synchronises before its uploads, recomputes stack_entries, and clears the AUTO pilot)
     if (st != GBL_OK) return st;

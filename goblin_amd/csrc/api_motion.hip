@@ -14,8 +14,11 @@
 
 namespace {
 
-gbl_status gbl_get_instances_impl(const gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_trs* out) {
-    if (!ctx || !out || static_cast<uint64_t>(first) + count > ctx->h_instances.size()) return GBL_ERR_INVALID;
+gbl_status gbl_get_instances_impl(const gbl_ctx* cctx, uint32_t first, uint32_t count, gbl_trs* out) {
+    if (!cctx || !out || static_cast<uint64_t>(first) + count > cctx->h_instances.size()) return GBL_ERR_INVALID;
+    gbl_ctx* ctx = const_cast<gbl_ctx*>(cctx);   // (the transforms' host copy is a cache of the device's after a device edit: refreshing it changes nothing a caller can see)
+    const gbl_status st = refresh_instance_mirror(ctx);
+    if (st != GBL_OK) return st;
     for (uint32_t i = 0; i < count; ++i) out[i] = ctx->h_instances[first + i].to_world;
     return GBL_OK;
 }
@@ -135,6 +138,8 @@ gbl_status gbl_render_motion_impl(gbl_ctx* ctx, const gbl_motion_params* p, cons
     bool any_moved = false;
     std::vector<unsigned char> staged;
     if (p->prev_to_world && count > 0) {
+        const gbl_status fresh = refresh_instance_mirror(ctx);   // (the current transforms are compared and composed on the host)
+        if (fresh != GBL_OK) return fresh;
         staged.assign(xf_bytes + flag_bytes, 0);
         float* xf = reinterpret_cast<float*>(staged.data());
         uint32_t* moved = reinterpret_cast<uint32_t*>(staged.data() + xf_bytes);

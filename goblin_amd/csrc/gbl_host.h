@@ -33,6 +33,14 @@ inline gbl_status make_orders_if(gbl_ctx* ctx, bool follows_ties) { return follo
 // caller has synchronised the device or knows it idle.  (api_geometry.hip)
 gbl_status refresh_mirror(gbl_ctx* ctx, uint32_t mesh);
 
+// h_instances' transforms brought up to the device's raw table, if a device instance edit left a range of them stale: one
+// device-to-host copy of that range (it waits for the device).  Every reader of h_instances[i].to_world calls it first:
+// gbl_get_instances, gbl_update_instances, the TLAS tail of the geometry edits, gbl_render_motion*.  (api_instances.hip)
+gbl_status refresh_instance_mirror(gbl_ctx* ctx);
+// ... and the other direction: h_instances[first .. first + count).to_world into the raw table, if the context has one yet
+// (a host instance edit after a device one).  (api_instances.hip)
+gbl_status write_instance_table(gbl_ctx* ctx, uint32_t first, uint32_t count);
+
 // GBL_OK when `p` is device or managed memory of the context's device whose allocation holds `bytes` from p on; GBL_ERR_INVALID
 // with "`who`: `what` ..." otherwise, the sticky error a plain host pointer leaves cleared.  Touches no device memory.  (api_geometry.hip)
 gbl_status check_device_pointer(gbl_ctx* ctx, const void* p, uint64_t bytes, const std::string& who, const char* what);

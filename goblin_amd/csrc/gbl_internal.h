@@ -113,6 +113,15 @@ struct gbl_ctx {
     std::vector<int32_t> rebuild_slot;       // per mesh: the first of the tri_count node records its rebuilt trees are written to; -1: none yet
     std::vector<uint32_t*> rebuild_idx;      // per mesh: its slice of h_indices on the device, uploaded at its first rebuild
     gbl_buf tree_stats;                      // three sums (root, node and triangle area), then two partial sums per workgroup (kernels/treestats.h)
+    // what the device-pointer instance entries keep (api_instances.hip, kernels/instances.h)
+    gbl_trs* d_trs = nullptr;                // the raw transforms per instance on the device: made from h_instances at the first device edit or
+                                             // gbl_get_instances_device, written by every instance edit after that
+    uint32_t trs_stale_first = 0, trs_stale_end = 0;   // h_instances[first .. end).to_world is older than d_trs (refresh_instance_mirror)
+    float* d_mesh_bounds = nullptr;          // mesh_lo / mesh_hi on the device, 6 floats per mesh ...
+    std::vector<float> mesh_bounds_sent;     // ... and the values last uploaded: a vertex edit or a rebuild changes mesh_lo / mesh_hi, the next
+                                             // device instance edit sees the difference and uploads again
+    gbl_buf inst_stage;                      // the refusal word, the edited instances' staged records and bounds, the merged bounds of a device TLAS
+    std::vector<DevInstance> need_instances; // shape and mesh per instance (transform edits change neither): what scene_stack_entries reads
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
@@ -210,6 +219,13 @@ void gbl_launch_vertices_check(const float* positions, const float* normals, uin
 void gbl_launch_mesh_bound(const float* positions, uint32_t vertex_count, unsigned long long* keys, float* bound, hipStream_t stream);
 void gbl_launch_pose_differs(const PoseList* list, uint32_t num_listed, uint32_t max_floats, const float* positions, uint32_t num_floats_total, uint32_t* differs,
                              hipStream_t stream);
+// kernels_instances.hip: the passes of the device-pointer instance entries (kernels/instances.h).  *refusal is all ones before the
+// launch; the staged records are written for the instances that are not refused.  gbl_build_tlas_device builds the TLAS over n >= 2
+// instance boxes into the context's builder scratch (ctx->lbvh_scratch) and writes nothing of the scene.
+void gbl_launch_inst_compose(const gbl_trs* d_trs, uint32_t first, uint32_t count, const DevInstance* live, const float* mesh_bounds, uint32_t num_meshes,
+                             bool refuse_box, DevInstance* out_inst, DevInstanceBound* out_bound, unsigned long long* refusal, hipStream_t stream);
+gbl_status gbl_build_tlas_device(gbl_ctx* ctx, const DevInstanceBound* d_bounds, uint32_t n, int32_t tlas_base, uint32_t capacity, const DevNode** d_nodes_out,
+                                 uint32_t* nodes_out, int* depth_out);
 gbl_status gbl_build_blas_device(gbl_ctx* ctx, const float* d_pos, const uint32_t* d_idx, uint32_t n, const float* lo, const float* hi,
                                  DevNode* d_nodes, int32_t node_base, DevTri* d_tris, uint32_t tri_base, uint32_t shade_base, uint32_t tri_flags,
                                  int32_t* root_out, uint32_t* nodes_out, int* depth_out);   // (its scratch is ctx->lbvh_scratch, grown on demand)

@@ -708,6 +708,21 @@ gbl_status validate_desc(const gbl_scene_desc* d, std::string* err) {
     return st;
 }
 
+// The TLAS over instance primitives (box, centre, id = instance index): what build_tlas and build_tlas_nodes share
+void tlas_over(std::vector<Prim>& iprims, int32_t tlas_base, std::vector<DevNode>* nodes, int32_t* root_out, int* depth_out) {
+    const int kTlasCap = 22;
+    nodes->clear();
+    *depth_out = 0;
+    *root_out = 0;
+    if (iprims.empty()) return;
+    Builder tb(iprims, 1, kTlasCap);
+    int root = tb.build(0, iprims.size(), 1);
+    Flat4 t4(tb, *nodes, tlas_base);
+    auto inst_ref = [&](uint32_t first, uint32_t) { return ~static_cast<int32_t>(iprims[first].id << 2); };
+    *root_out = t4.emit(root, 1, inst_ref);
+    *depth_out = t4.depth;
+}
+
 }  // namespace
 
 int scene_stack_entries(const std::vector<DevNode>& tlas, int32_t tlas_base, int32_t tlas_root, const std::vector<DevInstance>& instances,
@@ -718,7 +733,6 @@ int scene_stack_entries(const std::vector<DevNode>& tlas, int32_t tlas_base, int
 // Instances (transforms in the reference's float order, world boxes by Transform::onBBox) and the TLAS over them.
 // TLAS node k gets device index tlas_base + k; bound_lo/hi return the union of the instance boxes.
 gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err) {
-    const int kTlasCap = 22;
     out->instances.resize(in.count);
     out->instance_bounds.resize(in.count);
     out->nodes.clear();
@@ -756,17 +770,22 @@ gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err) {
         scene_bound.grow(p.box.hi);
     }
     store_bound(scene_bound, out->bound_lo, out->bound_hi);
-    out->depth = 0;
-    out->root = 0;
-    if (in.count > 0) {
-        Builder tb(iprims, 1, kTlasCap);
-        int root = tb.build(0, iprims.size(), 1);
-        Flat4 t4(tb, out->nodes, in.tlas_base);
-        auto inst_ref = [&](uint32_t first, uint32_t) { return ~static_cast<int32_t>(iprims[first].id << 2); };
-        out->root = t4.emit(root, 1, inst_ref);
-        out->depth = t4.depth;
-    }
+    tlas_over(iprims, in.tlas_base, &out->nodes, &out->root, &out->depth);
     return GBL_OK;
+}
+
+void build_tlas_nodes(const DevInstanceBound* bounds, uint32_t count, int32_t tlas_base, std::vector<DevNode>* nodes, int32_t* root, int* depth) {
+    std::vector<Prim> iprims(count);
+    for (uint32_t i = 0; i < count; ++i) {   // the primitives build_tlas makes: it stores exactly these boxes
+        Prim& p = iprims[i];
+        for (int k = 0; k < 3; ++k) {
+            p.box.lo[k] = bounds[i].lo[k];
+            p.box.hi[k] = bounds[i].hi[k];
+            p.c[k] = 0.5f * (p.box.lo[k] + p.box.hi[k]);
+        }
+        p.id = i;
+    }
+    tlas_over(iprims, tlas_base, nodes, root, depth);
 }
 
 bool pack_transform(const gbl_trs& to_world, uint32_t i, float m[12], float inv[12], std::string* err) {

@@ -78,6 +78,9 @@ struct TlasResult {
 };
 // Refuses (GBL_ERR_INVALID, *err set, *out unspecified) an instance whose transform the reference cannot invert.
 gbl_status build_tlas(const TlasInput& in, TlasResult* out, std::string* err);
+// build_tlas's tree alone, over instance world boxes composed elsewhere (gbl_update_instances_device composes them on the
+// device): fed the boxes build_tlas stores, it returns build_tlas's nodes, root and depth.  Cannot fail.
+void build_tlas_nodes(const DevInstanceBound* bounds, uint32_t count, int32_t tlas_base, std::vector<DevNode>* nodes, int32_t* root, int* depth);
 
 // The 3x4 rows of a transform and of its inverse as build_tlas composes them for DevInstance::m / inv (gbl_render_motion's
 // previous transforms).  false, *err set to build_tlas's refusal for instance i, when the reference cannot invert it.

@@ -69,8 +69,39 @@ class HipPathTracer:
         self.info = info
         self.window = tuple(info.window)
 
-    def update_instances(self, first, transforms):
-        """Move instances first.. to new (position, orientation wxyz, scale) transforms and rebuild the TLAS in place."""
+    def _device_transforms(self, t):
+        """The data pointer of ``t``, a contiguous float32 (n, 10) tensor on the tracer's device (its storage offset included);
+        ValueError for anything else.  An empty tensor has no pointer of its own and borrows one."""
+        torch = _torch()
+        if t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.shape[1] != 10 or not t.is_contiguous():
+            raise ValueError("transforms must be a contiguous float32 (n, 10) tensor on %s, got %s %s on %s%s" %
+                             (self.device, t.dtype, tuple(t.shape), t.device, "" if t.is_contiguous() else ", not contiguous"))
+        if t.shape[0] == 0:
+            self._one_transform = getattr(self, "_one_transform", None)
+            if self._one_transform is None:
+                self._one_transform = torch.zeros((1, 10), dtype=torch.float32, device=self.device)
+            return self._one_transform.data_ptr()
+        return t.data_ptr()
+
+    def update_instances(self, first, transforms, device_tlas=False):
+        """Move instances first.. to new (position, orientation wxyz, scale) transforms and rebuild the TLAS in place.
+
+        A contiguous float32 (n, 10) torch tensor on the tracer's device -- columns position, orientation wxyz, scale, which is
+        gbl_trs' layout -- is read where it lies (gbl_update_instances_device; a slice with a storage offset is fine); any
+        other tensor is a ValueError.  ``device_tlas``: build the TLAS on the device too (GBL_INSTANCES_DEVICE_TLAS: faster
+        to build for many instances, slower to trace); a list is uploaded to a tensor first then."""
+        if hasattr(transforms, "data_ptr") or device_tlas:
+            torch = _torch()
+            if not hasattr(transforms, "data_ptr"):
+                rows = np.array([list(pos) + list(quat) + list(scale) for pos, quat, scale in transforms], np.float32).reshape(-1, 10)
+                transforms = torch.from_numpy(rows).to(self.device)
+            ptr = self._device_transforms(transforms)
+            st = self.lib.gbl_update_instances_device(self.handle, int(first), transforms.shape[0], ptr,
+                                                      _abi.GBL_INSTANCES_DEVICE_TLAS if device_tlas else 0)
+            if st != _abi.GBL_OK:
+                raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+            self.lib.gbl_get_info(self.handle, C.byref(self.info))
+            return
         arr = (_abi.gbl_trs * len(transforms))()
         for i, (pos, quat, scale) in enumerate(transforms):
             arr[i].position[:] = pos
@@ -81,10 +112,18 @@ class HipPathTracer:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         self.lib.gbl_get_info(self.handle, C.byref(self.info))
 
-    def instances(self):
+    def instances(self, device=False):
         """The transforms the context holds now (gbl_get_instances): a list of (position, orientation wxyz, scale) tuples, one per
-        instance -- the scene's at first, the edited ones after ``update_instances``.  What ``motion`` takes as ``prev_instances``."""
+        instance -- the scene's at first, the edited ones after ``update_instances``.  What ``motion`` takes as ``prev_instances``.
+        ``device=True``: an (n, 10) float32 tensor on the tracer's device, copied device to device (gbl_get_instances_device)."""
         n = int(self.info.instances)
+        if device:
+            torch = _torch()
+            out = torch.empty((max(n, 1), 10), dtype=torch.float32, device=self.device)
+            st = self.lib.gbl_get_instances_device(self.handle, 0, n, out.data_ptr())
+            if st != _abi.GBL_OK:
+                raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+            return out[:n]
         arr = (_abi.gbl_trs * max(n, 1))()
         st = self.lib.gbl_get_instances(self.handle, 0, n, arr)
         if st != _abi.GBL_OK:
@@ -218,6 +257,24 @@ class HipPathTracer:
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return out
+
+    _INSTANCE = np.dtype([("m", "<f4", 12), ("inv", "<f4", 12), ("root", "<i4"), ("material", "<i4"), ("area_light", "<i4"), ("mesh", "<i4"),
+                          ("shape", "<u4"), ("radius", "<f4"), ("is_mask", "<u4"), ("pad", "<i4")])
+    _INSTANCE_BOUND = np.dtype([("lo", "<f4", 3), ("hi", "<f4", 3)])
+
+    def _instances_raw(self, first=0, count=None):
+        """The device's instance records and instance bounds of [first, first + count) read back (gbl_selftest_instances) as
+        numpy structured arrays, with the TLAS root and the traversal stack entries the context holds now: a dict of records,
+        bounds, total, tlas_root, stack_entries.  For tests."""
+        total, root, entries = C.c_uint64(), C.c_int32(), C.c_int32()
+        st = self.lib.gbl_selftest_instances(self.handle, 0, 0, None, None, C.byref(total), C.byref(root), C.byref(entries))
+        if st == _abi.GBL_OK:
+            count = total.value - first if count is None else count
+            records, bounds = np.zeros(max(count, 0), self._INSTANCE), np.zeros(max(count, 0), self._INSTANCE_BOUND)
+            st = self.lib.gbl_selftest_instances(self.handle, first, count, records.ctypes.data, bounds.ctypes.data, None, None, None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return {"records": records, "bounds": bounds, "total": total.value, "tlas_root": root.value, "stack_entries": entries.value}
 
     def camera(self):
         """The camera description last set (gbl_get_camera): a gbl_camera, the scene's at first."""

@@ -727,6 +727,45 @@ gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, co
  * context holds no frame state.  GBL_ERR_INVALID for a NULL argument or a range out of bounds. */
 gbl_status gbl_get_instances(const gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_trs* out);
 
+/* gbl_update_instances with the transforms read from DEVICE memory: what a rigid-body or particle step on the GPU leaves behind
+ * goes into the context without a trip through the host.  d_to_world holds `count` gbl_trs records of 40 bytes.
+ *  - flags == 0: after the call every device table -- the instance records and bounds, the TLAS's used records, and gbl_info --
+ *    is byte for byte what gbl_update_instances leaves when fed the same floats.  Order of the call: synchronise; one kernel
+ *    composes the edited instances' m / inv and world boxes into staging and folds refusals into a word; 8 bytes are read back;
+ *    the instance bounds are read back and the TLAS is built on the host as in every edit; upload and commit; synchronise.
+ *  - GBL_INSTANCES_DEVICE_TLAS: the TLAS is built on the device over the instance bounds by the linear builder
+ *    (gbl_create_ex's GBL_CREATE_DEVICE_BVH builder, a leaf being one instance) and lands in the TLAS's reserved node records.
+ *    What crosses the bus: the refusal word, 8 bytes of counters per level of the tree, and the tree's used records (64 bytes
+ *    per node, at most one per instance), which the exact traversal-stack rule is evaluated over.  A render under the tie rule
+ *    (exact_ties, replay, stream, instrumented, Whitted, every EXT build) equals, bit for bit, that of a fresh context of the
+ *    edited scene; the linear tree is faster to build and slower to trace than the host's.  Any later host-tail edit
+ *    (gbl_update_instances, gbl_update_vertices*, gbl_rebuild_mesh) puts a host-built TLAS back.  A context with fewer than
+ *    two instances ignores the flag.
+ *  - The context's host copy of the transforms becomes a mirror: the edit marks its range stale, and gbl_get_instances,
+ *    gbl_update_instances, the geometry edits and gbl_render_motion* refresh it with one download of the stale range when they
+ *    need it.  The raw transforms are kept in a device table made at the first call of this entry or of
+ *    gbl_get_instances_device and written by every instance edit after that.
+ * Refusals, the context untouched: GBL_ERR_INVALID for a NULL pointer, unknown bits in flags, a pointer that is not device or
+ * managed memory of the context's device, an allocation that ends before 40 * count bytes; gbl_update_instances' own with its
+ * messages (range out of bounds, a directional or image based light, an instance that carries an area light); then, met by the
+ * kernel: GBL_ERR_INVALID for a transform with a float that is not finite (the host entry does not check this), naming the lowest
+ * such instance, and, when no transform is non-finite, gbl_update_instances' |det| < 1e-5 refusal for the lowest such instance.
+ * With GBL_INSTANCES_DEVICE_TLAS also GBL_ERR_INVALID for a world bound that overflows a float.  count == 0 with a valid
+ * pointer is GBL_OK and changes nothing. */
+#define GBL_INSTANCES_DEVICE_TLAS 1u
+gbl_status gbl_update_instances_device(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* d_to_world /* device, count records of 40 B */,
+                                       uint32_t flags);
+/* gbl_get_instances into DEVICE memory: a device-to-device copy from the context's raw transform table, complete when the call
+ * returns.  Before any device edit the table is uploaded from the host's values.  GBL_ERR_INVALID for a NULL argument, a range
+ * out of bounds and the pointer refusals above. */
+gbl_status gbl_get_instances_device(gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_trs* d_out /* device */);
+/* Self-test hook: the DevInstance records (128 B: m[12], inv[12], root, material, area_light, mesh, shape, radius, is_mask, pad)
+ * and the DevInstanceBound records (24 B: lo[3], hi[3]) of instances [first, first + count) to host memory, and *total (the
+ * instance count), *tlas_root and *stack_entries as the context holds them now.  Any out pointer may be NULL.  Synchronises the
+ * device when it copies. */
+gbl_status gbl_selftest_instances(gbl_ctx* ctx, uint64_t first, uint64_t count, void* records_out, void* bounds_out, uint64_t* total, int32_t* tlas_root,
+                                  int32_t* stack_entries);
+
 /* Vertex edit: give vertices [first, first + count) of triangle mesh `mesh` (gbl_scene_desc::meshes index; vertex numbers are the
  * mesh's own, 0 .. vertex_count) new object-space positions, and new normals if `normals` is not NULL.  The mesh's BLAS is
  * refitted on the device in place; nothing is rebuilt on the host but the TLAS.
