@@ -188,6 +188,19 @@ class gbl_tree_stats(C.Structure):
                 ("root_area", C.c_double), ("node_area", C.c_double), ("tri_area", C.c_double)]
 
 
+class gbl_ray(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("mint", C.c_float), ("d", C.c_float * 3), ("maxt", C.c_float)]
+
+
+class gbl_ray_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("instance", C.c_int32), ("primitive", C.c_uint32),
+                ("n", C.c_float * 3)]
+
+
+GBL_QUERY_CLOSEST, GBL_QUERY_ANY = 0, 1                   # gbl_trace_rays kind
+GBL_QUERY_EXACT_TIES, GBL_QUERY_SHADING_NORMAL = 1, 2     # gbl_trace_rays flags
+
+
 class gbl_info(C.Structure):
     _fields_ = [("xres", C.c_int32), ("yres", C.c_int32), ("window", C.c_int32 * 4), ("blas_nodes", C.c_uint64),
                 ("tlas_nodes", C.c_uint64), ("triangles", C.c_uint64), ("instances", C.c_uint64),
@@ -202,7 +215,7 @@ HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
 GBL_INSTANCES_DEVICE_TLAS = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_rebuild_mesh", "gbl_mesh_tree_stats", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_update_instances_device", "gbl_get_instances_device", "gbl_selftest_instances", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_rebuild_mesh", "gbl_mesh_tree_stats", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_update_instances_device", "gbl_get_instances_device", "gbl_selftest_instances", "gbl_trace_rays", "gbl_selftest_query", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
                "gbl_aov_resolve_depth", "gbl_film_variance", "gbl_film_denoise", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
@@ -312,6 +325,8 @@ def hip_lib():
         lib.gbl_get_instances_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.gbl_selftest_instances.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int32)]
+        lib.gbl_trace_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.gbl_selftest_query.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.gbl_update_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
         lib.gbl_get_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
         lib.gbl_get_info.argtypes = [C.c_void_p, C.POINTER(gbl_info)]

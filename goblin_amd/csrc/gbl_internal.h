@@ -8,6 +8,7 @@
 
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/goblin_hip.h"
@@ -19,6 +20,7 @@
 #include "kernels/motion_args.h"
 #include "kernels/refit_args.h"
 #include "kernels/vertices_args.h"
+#include "kernels/query_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -122,6 +124,10 @@ struct gbl_ctx {
                                              // device instance edit sees the difference and uploads again
     gbl_buf inst_stage;                      // the refusal word, the edited instances' staged records and bounds, the merged bounds of a device TLAS
     std::vector<DevInstance> need_instances; // shape and mesh per instance (transform edits change neither): what scene_stack_entries reads
+    // what gbl_trace_rays keeps (api_query.hip, kernels/query.h)
+    uint32_t* d_mesh_tri_offset = nullptr;   // gbl_mesh::tri_offset per mesh on the device, made at the first query: a hit's primitive number
+    gbl_buf query_spill;                     // the query kernels' stack levels beyond LDS, one column per thread of the largest grid
+    std::map<std::pair<const void*, size_t>, int> query_occupancy;   // resident workgroups per CU by (kernel, dynamic LDS bytes), asked once each
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
@@ -145,6 +151,7 @@ typedef void (*gbl_wf_kernel)(DevScene, RenderArgs, WfArgs);
 typedef void (*gbl_li_kernel)(DevScene, RenderArgs, float4*);
 typedef void (*gbl_aov_kernel)(DevScene, RenderArgs, AovArgs);
 typedef void (*gbl_motion_kernel)(DevScene, MotionArgs);
+typedef void (*gbl_query_kernel)(DevScene, QueryArgs);
 
 // kernels_path.hip: the persistent megakernel and the AO kernel (kernels/render_kernels.h), native / replay samplers
 gbl_render_kernel gbl_kernel_path(bool replay, bool stats, bool ext, bool exact_ties = false);
@@ -204,6 +211,11 @@ gbl_motion_kernel gbl_kernel_motion(bool packet, bool ext, bool deform = false);
 void gbl_launch_temporal_accumulate_motion(bool spatial, const float4* cl, const float4* nz, const uint32_t* fl, const float* variance,
                                            const float* history_in, float* history_out, float* film_out, float* variance_out, const float* motion,
                                            const TemporalArgs& a, hipStream_t stream);
+// kernels_query.hip: gbl_trace_rays' kernels (kernels/query.h) -- any-hit or closest-hit, lean or EXT, with or without the tie rule,
+// with or without the shading normal (closest-hit only: nullptr for any && normal).  gbl_query_plain: the unit was built as the
+// one-ray-per-lane measurement form (-DGBL_QUERY_PLAIN), which takes the whole stack in LDS and no hot prefix.
+gbl_query_kernel gbl_kernel_query(bool any, bool ext, bool ties, bool normal);
+bool gbl_query_plain(void);
 // kernels_refit.hip: the passes of gbl_update_vertices (kernels/refit.h)
 void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade* tri_shade, const float* pos, uint32_t num_vertices, uint32_t first,
                            uint32_t count, hipStream_t stream);

@@ -302,6 +302,52 @@ class HipPathTracer:
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
 
+    def _query_flags(self, kind, exact_ties, normals):
+        if kind not in ("closest", "any"):
+            raise ValueError("kind must be 'closest' or 'any', got %r" % (kind,))
+        if normals and kind == "any":
+            raise ValueError("normals need kind='closest': an any-hit query has no hit to shade")
+        return (_abi.GBL_QUERY_ANY if kind == "any" else _abi.GBL_QUERY_CLOSEST,
+                (_abi.GBL_QUERY_EXACT_TIES if exact_ties else 0) | (_abi.GBL_QUERY_SHADING_NORMAL if normals else 0))
+
+    def trace(self, rays, kind="closest", exact_ties=False, normals=False, out=None, stream=None, _max_workgroups=None):
+        """Scene queries for a batch of rays (gbl_trace_rays) against the scene as edited so far.
+
+        ``rays``: a contiguous float32 (n, 8) tensor on the tracer's device -- columns origin, mint, direction, maxt, which is
+        gbl_ray's layout -- read where it lies.  The direction need not be normalised; t is in its units.
+
+        kind="closest": a dict of views over one (n, 8) float32 output tensor (``out``, or a new one; the dict's "records"):
+        t (-1: miss), b1, b2, instance (int32, -1: miss), primitive (int32: the triangle's number within its mesh), normal
+        ((n, 3): the world-space shading normal with ``normals``, zeros without).  kind="any": an (n,) uint8 tensor, 1 occluded.
+        ``exact_ties``: the reference's answer bit for bit.  Queued on ``stream`` (a torch stream; the current one by
+        default); does not synchronise."""
+        torch = _torch()
+        k, flags = self._query_flags(kind, exact_ties, normals)
+        if rays.dtype != torch.float32 or rays.device != self.device or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous float32 (n, 8) tensor on %s, got %s %s on %s%s" %
+                             (self.device, rays.dtype, tuple(rays.shape), rays.device, "" if rays.is_contiguous() else ", not contiguous"))
+        n = rays.shape[0]
+        want = (n,) if kind == "any" else (n, 8)
+        dtype = torch.uint8 if kind == "any" else torch.float32
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if out is None:
+            with torch.cuda.stream(s):   # (the caching allocator ties the block to the stream that uses it)
+                out = torch.empty(want, dtype=dtype, device=self.device)
+        elif out.dtype != dtype or out.device != self.device or tuple(out.shape) != want or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s %s tensor on %s" % (dtype, want, self.device))
+        if n > 0:
+            if _max_workgroups is None:
+                st = self.lib.gbl_trace_rays(self.handle, k, rays.data_ptr(), n, out.data_ptr(), flags, s.cuda_stream)
+            else:
+                st = self.lib.gbl_selftest_query(self.handle, k, rays.data_ptr(), n, out.data_ptr(), flags, int(_max_workgroups))
+            if st != _abi.GBL_OK:
+                raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        if kind == "any":
+            return out
+        ints = out.view(torch.int32)
+        return {"records": out, "t": out[:, 0], "b1": out[:, 1], "b2": out[:, 2], "instance": ints[:, 3], "primitive": ints[:, 4],
+                "normal": out[:, 5:8]}
+
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
         if h:

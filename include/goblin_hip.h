@@ -884,6 +884,56 @@ gbl_status gbl_selftest_geometry(gbl_ctx* ctx, int table, uint64_t first, uint64
 gbl_status gbl_update_camera(gbl_ctx* ctx, const gbl_camera* camera);
 gbl_status gbl_get_camera(const gbl_ctx* ctx, gbl_camera* out);
 
+/* Scene queries: Scene::intersect (GBL_QUERY_CLOSEST) or Scene::occluded (GBL_QUERY_ANY) for n caller rays in DEVICE memory,
+ * against the context as it is now -- every gbl_update_instances*, gbl_update_vertices*, gbl_rebuild_mesh edit taken so far is
+ * seen.  What a simulation step on the GPU asks between two edits: collision probes, ground snapping, line of sight, picking,
+ * probe and lightmap baking, custom AO.
+ *  - A ray is {o, mint, d, maxt}.  d need not be normalised and t is in units of d: o = p, d = q - p, mint = eps, maxt = 1 - eps
+ *    asks "does q see p".  maxt = +inf is allowed.  The interval is inclusive, like the reference's.
+ *  - GBL_QUERY_CLOSEST writes n gbl_ray_hit records.  On a hit: t, b1, b2 as the triangle test left them; instance indexes
+ *    gbl_scene_desc.instances; primitive is the triangle's number within its own mesh in the scene description's order (it does
+ *    not change when a builder or gbl_rebuild_mesh reorders the triangle table); a sphere or a disk reports primitive 0 and
+ *    b1 = b2 = 0.  On a miss: t = -1, instance = -1, everything else 0.  The hit point is o + t d, or the mesh's
+ *    v0 + b1 (v1 - v0) + b2 (v2 - v0) taken to world space.
+ *  - GBL_QUERY_ANY writes n bytes: 1 occluded, 0 not.
+ *  - GBL_QUERY_SHADING_NORMAL (closest only): n is the world-space shading normal of the hit -- interpolated vertex normals
+ *    where the mesh has them, bump and normal maps applied, unit length, NOT flipped towards the ray.  Without the flag n is
+ *    zeros and no fragment is made.
+ *  - GBL_QUERY_EXACT_TIES: the reference's answer bit for bit, as a render with exact_ties: its visiting order decides which of
+ *    two triangles met at exactly the same t is reported, and a triangle its own (not watertight) box tests would pass by is
+ *    not accepted.  Without the flag the nearest accepted triangle is reported, whichever of two tied ones was tested last;
+ *    never a hit farther than the exact one's, and never a miss where the exact query hits.  Which builds read the tie order
+ *    (gbl_update_vertices_device): the two exact ones only.  A query without the flag -- on a scene of the headline feature set
+ *    or on one with analytic shapes -- does not, and leaves a deferred order pending.
+ *  - An invalid ray -- a NaN among its eight floats, an infinite component of o or d, d all zeros, !(mint <= maxt) -- reports a
+ *    miss (unoccluded) and enters no traversal.  No input makes the call spin: traversal is bounded by its stack.
+ *  - Asynchronous on `stream`; no host synchronisation but these: the one that makes a pending tie order for an exact query; in a
+ *    context's first query, one small upload and the allocation of the stack backing; and, in the first query after an edit has
+ *    deepened the tree past that backing, its reallocation (a free and an allocation, which wait for the device).  The per-lane
+ *    stacks beyond 16 levels live in that buffer of the context: queries of one context are queued on one stream at a time, like
+ *    its renders.
+ *  - Limit: queries are unfiltered.  The surface of a mask material counts as a surface (the reference's isOpaque filter, which
+ *    its shadow rays use, is not offered); see DESIGN.md 9.
+ * Refusals, nothing launched: GBL_ERR_INVALID for a NULL ctx, a NULL pointer with n > 0, an unknown kind, unknown bits in flags,
+ * GBL_QUERY_SHADING_NORMAL with GBL_QUERY_ANY, a pointer that is not device or managed memory of the context's device (a plain
+ * host pointer is refused before anything reads it) or whose allocation ends before 32 n bytes (n bytes for the any-hit
+ * output), and d_out overlapping d_rays; GBL_ERR_UNSUPPORTED for n >= 2^32 (the kernel keeps 32-bit ray indices).  n == 0 is
+ * GBL_OK and does nothing, whatever the pointers. */
+typedef struct gbl_ray     { float o[3]; float mint; float d[3]; float maxt; } gbl_ray;      /* 32 B: two 16-byte loads */
+typedef struct gbl_ray_hit { float t, b1, b2; int32_t instance; uint32_t primitive; float n[3]; } gbl_ray_hit; /* 32 B */
+#define GBL_QUERY_CLOSEST 0u      /* Scene::intersect */
+#define GBL_QUERY_ANY     1u      /* Scene::occluded  */
+#define GBL_QUERY_EXACT_TIES      1u   /* flags */
+#define GBL_QUERY_SHADING_NORMAL  2u
+gbl_status gbl_trace_rays(gbl_ctx* ctx, uint32_t kind, const gbl_ray* d_rays, uint64_t n,
+                          void* d_out /* CLOSEST: n gbl_ray_hit; ANY: n bytes, 1 = occluded */,
+                          uint32_t flags, void* stream);
+/* Self-test hook: gbl_trace_rays on the default stream with its persistent grid capped at max_workgroups (0: no cap) and a
+ * device synchronise at the end.  With one workgroup each wave walks many 64-ray regions at a few thousand rays: the refill
+ * path a plain call only reaches at hundreds of thousands of rays. */
+gbl_status gbl_selftest_query(gbl_ctx* ctx, uint32_t kind, const gbl_ray* d_rays, uint64_t n, void* d_out, uint32_t flags,
+                              uint32_t max_workgroups);
+
 /* Self-test hook: the device's sinf / cosf (glibc's algorithm restated, kernels/refmath.h) on n device floats. */
 gbl_status gbl_selftest_sincos(gbl_ctx* ctx, const float* in, float* sin_out, float* cos_out, uint64_t n);
 /* Self-test hook: out[i] = fn(a[i] [, b[i]]) on n device floats, fn one of the libm functions the reference's sampling code
