@@ -81,6 +81,27 @@ gbl_status rebuild_tlas(gbl_ctx* ctx, std::vector<gbl_instance>& edited, const c
     return GBL_OK;
 }
 
+gbl_status refuse_scene_bound_edit(gbl_ctx* ctx, const char* who) {
+    if (!ctx->has_directional) return GBL_OK;
+    return fail(ctx, GBL_ERR_UNSUPPORTED, std::string(who) + ": a directional or image based light's power (and the image based light's sampling sphere) "
+                                          "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead");
+}
+
+gbl_status move_instances(gbl_ctx* ctx, const uint32_t* which, uint32_t count, const gbl_trs* to_world, const char* who) {
+    gbl_status st = refresh_instance_mirror(ctx);   // (a device instance edit may have left the transforms' host copy behind)
+    if (st != GBL_OK) return st;
+    std::vector<gbl_instance> edited = ctx->h_instances;
+    for (uint32_t i = 0; i < count; ++i) edited[which[i]].to_world = to_world[i];
+    if ((st = rebuild_tlas(ctx, edited, who)) != GBL_OK) return st;
+    for (uint32_t i = 0; i < count;) {   // the raw table, run by run
+        uint32_t end = i + 1;
+        while (end < count && which[end] == which[end - 1] + 1) ++end;
+        if ((st = write_instance_table(ctx, which[i], end - i)) != GBL_OK) return st;
+        i = end;
+    }
+    return GBL_OK;
+}
+
 namespace {
 thread_local std::string g_create_error;
 
@@ -246,6 +267,17 @@ static gbl_status gbl_create_ex_impl(const gbl_scene_desc* desc, int device, uin
     sc.num_instances = static_cast<int32_t>(packed.instances.size());
     sc.num_lights = static_cast<int32_t>(packed.lights.size());
     for (const DevLight& l : packed.lights) ctx->h_light_slots.push_back(l.wh_n);
+    // what gbl_update_lights needs (api_lights.hip)
+    ctx->h_lights.assign(desc->lights, desc->lights + desc->num_lights);
+    ctx->h_dev_lights = packed.lights;
+    ctx->h_light_power = packed.light_power;
+    ctx->h_light_cdf = packed.light_cdf;
+    ctx->h_light_pick_pdf = packed.light_pick_pdf;
+    memcpy(ctx->bound_lo, packed.bound_lo, sizeof(ctx->bound_lo));
+    memcpy(ctx->bound_hi, packed.bound_hi, sizeof(ctx->bound_hi));
+    ctx->light_instances.assign(desc->num_lights, std::vector<uint32_t>());
+    for (uint32_t i = 0; i < desc->num_instances; ++i)
+        if (desc->instances[i].area_light >= 0) ctx->light_instances[desc->instances[i].area_light].push_back(i);
     sc.stack_entries = packed.stack_entries;
     sc.extended = packed.extended;
     sc.has_masks = packed.has_masks;
@@ -320,23 +352,17 @@ static gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32
         ctx->error = "gbl_update_instances: instance range out of bounds";
         return GBL_ERR_INVALID;
     }
-    if (ctx->has_directional) {
-        ctx->error = "gbl_update_instances: a directional or image based light's power (and the image based light's sampling sphere) "
-                     "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead";
-        return GBL_ERR_UNSUPPORTED;
-    }
+    gbl_status st = refuse_scene_bound_edit(ctx, "gbl_update_instances");
+    if (st != GBL_OK) return st;
     for (uint32_t i = 0; i < count; ++i)
         if (ctx->h_instances[first + i].area_light >= 0) {
             ctx->error = "gbl_update_instances: instance " + std::to_string(first + i) + " carries an area light, whose own transform would "
                          "have to move with it; re-create the context instead";
             return GBL_ERR_UNSUPPORTED;
         }
-    gbl_status st = refresh_instance_mirror(ctx);   // (a device instance edit may have left the transforms' host copy behind)
-    if (st != GBL_OK) return st;
-    std::vector<gbl_instance> edited = ctx->h_instances;
-    for (uint32_t i = 0; i < count; ++i) edited[first + i].to_world = to_world[i];
-    if ((st = rebuild_tlas(ctx, edited, "gbl_update_instances")) != GBL_OK) return st;
-    return write_instance_table(ctx, first, count);
+    std::vector<uint32_t> which(count);
+    for (uint32_t i = 0; i < count; ++i) which[i] = first + i;
+    return move_instances(ctx, which.data(), count, to_world, "gbl_update_instances");
 }
 gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
     return gbl_guard([&] { return gbl_update_instances_impl(ctx, first, count, to_world); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
@@ -382,6 +408,9 @@ void gbl_destroy(gbl_ctx* ctx) {
     if (ctx->wf_ev_shadow) (void)hipEventDestroy(ctx->wf_ev_shadow);
     if (ctx->wf_aux) (void)hipStreamDestroy(ctx->wf_aux);
     if (ctx->wf_host_flags) (void)hipHostFree(ctx->wf_host_flags);
+    for (hipEvent_t ev : ctx->light_ev)
+        if (ev) (void)hipEventDestroy(ev);   // (hipHostFree below waits for whatever upload still reads the staging)
+    if (ctx->light_stage) (void)hipHostFree(ctx->light_stage);
     for (int i = 0; i < gbl_ctx::kTimingRing; ++i)
         for (int k = 0; k < 3; ++k)
             if (ctx->t_ev[i][k]) (void)hipEventDestroy(ctx->t_ev[i][k]);

@@ -115,9 +115,7 @@ gbl_status gbl_update_instances_device_impl(gbl_ctx* ctx, uint32_t first, uint32
     if (flags & ~GBL_INSTANCES_DEVICE_TLAS) return fail(ctx, GBL_ERR_INVALID, "gbl_update_instances_device: unknown bits in flags");
     const size_t n = ctx->h_instances.size();
     if (static_cast<uint64_t>(first) + count > n) return fail(ctx, GBL_ERR_INVALID, "gbl_update_instances: instance range out of bounds");
-    if (ctx->has_directional)
-        return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_instances: a directional or image based light's power (and the image based light's sampling sphere) "
-                                              "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead");
+    if (gbl_status bound = refuse_scene_bound_edit(ctx, "gbl_update_instances"); bound != GBL_OK) return bound;
     for (uint32_t i = 0; i < count; ++i)
         if (ctx->h_instances[first + i].area_light >= 0)
             return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_instances: instance " + std::to_string(first + i) + " carries an area light, whose own transform would "

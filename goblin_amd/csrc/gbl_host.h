@@ -1,5 +1,5 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
-// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_query.hip) share.  No kernel header is needed to read it.
+// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip) share.  No kernel header is needed to read it.
 #pragma once
 #include <string>
 
@@ -21,6 +21,14 @@ gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what);
 // stack_entries, gbl_info's TLAS fields, the AUTO pilot's reset, and `instances` becomes the context's own.  `who` starts the
 // error messages.  A refusal (build_tlas's, or a TLAS beyond the reserved nodes) leaves the context untouched.  (api_context.hip)
 gbl_status rebuild_tlas(gbl_ctx* ctx, std::vector<gbl_instance>& instances, const char* who);
+
+// GBL_ERR_UNSUPPORTED with "`who`: a directional or image based light's power ..." in a scene with a light sized by the scene
+// bound, GBL_OK otherwise: what every edit that can move the bound asks first.  (api_context.hip)
+gbl_status refuse_scene_bound_edit(gbl_ctx* ctx, const char* who);
+// Instances which[0 .. count) take to_world[0 .. count): the host mirror refreshed, rebuild_tlas over the edited list, and the raw
+// transform table where the context has one.  Makes no refusal of its own: gbl_update_instances keeps an instance that carries an
+// area light out of it, gbl_update_lights moves exactly those, together with their light.  (api_context.hip)
+gbl_status move_instances(gbl_ctx* ctx, const uint32_t* which, uint32_t count, const gbl_trs* to_world, const char* who);
 
 // The tie order of every mesh a deferred device edit left pending (gbl_update_vertices_device with GBL_VERTICES_DEFER_ORDER):
 // mirror refreshed, mesh_reference_order on the host, the mesh's tri_order slice uploaded, behind a device synchronisation.

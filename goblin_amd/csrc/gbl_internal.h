@@ -128,6 +128,18 @@ struct gbl_ctx {
     uint32_t* d_mesh_tri_offset = nullptr;   // gbl_mesh::tri_offset per mesh on the device, made at the first query: a hit's primitive number
     gbl_buf query_spill;                     // the query kernels' stack levels beyond LDS, one column per thread of the largest grid
     std::map<std::pair<const void*, size_t>, int> query_occupancy;   // resident workgroups per CU by (kernel, dynamic LDS bytes), asked once each
+    // what gbl_update_lights needs to pack the light tables again (api_lights.hip, scene_prep.h repack_lights)
+    std::vector<gbl_light> h_lights;         // the description last set: gbl_create's at first (gbl_get_lights)
+    std::vector<DevLight> h_dev_lights;      // the device's light records, light_cdf and light_pick_pdf as last queued ...
+    std::vector<float> h_light_power, h_light_cdf, h_light_pick_pdf;   // ... and the powers the two distributions are made of
+    float bound_lo[3] = {}, bound_hi[3] = {};   // gbl_create's scene bound: read for a directional light's power only, and every edit that
+                                             // could change the bound is refused in a scene with such a light
+    std::vector<std::vector<uint32_t>> light_instances;   // per light: the instances whose area_light names it
+    // ... and its pinned staging: kLightSlots copies of the three tables, each with the event of the upload that last read it
+    static const int kLightSlots = 4;
+    unsigned char* light_stage = nullptr;
+    hipEvent_t light_ev[4] = {};
+    unsigned light_edits = 0;
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings

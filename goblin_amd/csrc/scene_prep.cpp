@@ -1164,7 +1164,7 @@ const float kOne[3] = {1.0f, 1.0f, 1.0f}, kZero[3] = {0.0f, 0.0f, 0.0f};
 
 // Spot and directional lights: the axis the light works with is the third column of the matrix of its orientation.  The
 // spot light's ctor normalises the direction, the directional light's does not (GoblinLight.cpp:136-143).
-float pack_aimed_light(const gbl_light& gl, const Aabb& scene_bound, PackedScene* out, DevLight* dl) {
+float pack_aimed_light(const gbl_light& gl, const Aabb& scene_bound, DevLight* dl) {
     const bool spot = gl.type == GBL_LIGHT_SPOT;
     float dir[3] = {gl.direction[0], gl.direction[1], gl.direction[2]};
     if (spot) {
@@ -1177,7 +1177,6 @@ float pack_aimed_light(const gbl_light& gl, const Aabb& scene_bound, PackedScene
     for (int k = 0; k < 3; ++k) dl->axis[k] = t.m.v[k][0] * 0.0f + t.m.v[k][1] * 0.0f + t.m.v[k][2] * 1.0f;
     if (spot) return power_of(dl->color, kTwoPi, 1.0f - 0.5f * (dl->cos_max + dl->cos_falloff));
     // DirectionalLight::power (:203-210): radius^2 * PI * radiance over Scene::getBoundingSphere
-    out->extended = 1;
     const float radius = bounding_radius(scene_bound);
     return power_of(dl->color, radius * radius * kPi);
 }
@@ -1213,11 +1212,9 @@ float pack_light_tris(const gbl_scene_desc& d, const gbl_mesh& gm, PackedScene* 
     return sum;
 }
 
-// AreaLight over a mesh's triangles or, as a GeometrySet over one intersectable geometry (GoblinLight.cpp:289-303), a sphere / disk
-float pack_area_light(const gbl_scene_desc& d, const gbl_light& gl, PackedScene* out, DevLight* dl) {
-    const Trs t = compose(gl.to_world.position, gl.to_world.orientation, gl.to_world.scale);
-    store3x4(t.m, dl->m);
-    store3x4(t.inv, dl->inv);
+// AreaLight over a mesh's triangles or, as a GeometrySet over one intersectable geometry (GoblinLight.cpp:289-303), a sphere / disk:
+// the emitting geometry, which no light edit changes ...
+void attach_area_geometry(const gbl_scene_desc& d, const gbl_light& gl, PackedScene* out, DevLight* dl) {
     const gbl_mesh& gm = d.meshes[gl.mesh];
     if (gm.shape != GBL_SHAPE_MESH) {
         out->extended = 1;
@@ -1227,6 +1224,12 @@ float pack_area_light(const gbl_scene_desc& d, const gbl_light& gl, PackedScene*
     } else {
         dl->sum_area = pack_light_tris(d, gm, out, dl);
     }
+}
+// ... and its transform, with the power over the world area
+float pack_area_light(const gbl_light& gl, DevLight* dl) {
+    const Trs t = compose(gl.to_world.position, gl.to_world.orientation, gl.to_world.scale);
+    store3x4(t.m, dl->m);
+    store3x4(t.inv, dl->inv);
     const float world_area = dl->sum_area * (gl.to_world.scale[0] * gl.to_world.scale[1]);
     return power_of(dl->color, kPi, world_area);
 }
@@ -1277,11 +1280,8 @@ void pack_ibl_distribution(const IblTexels& tx, PackedScene* out, DevLight* dl) 
     out->ibl_dist.insert(out->ibl_dist.end(), rows_block.begin(), rows_block.end());
 }
 
-// ImageBasedLight's constructor (GoblinLight.cpp:464-508)
-float pack_ibl_light(const gbl_scene_desc& d, const gbl_light& gl, const Aabb& scene_bound, PackedScene* out, DevLight* dl) {
-    out->extended = 1;
-    out->has_ibl = 1;
-    dl->image = gl.image;
+// ImageBasedLight's constructor (GoblinLight.cpp:464-508): the rotation, which an edit may change ...
+void pack_ibl_rotation(const gbl_light& gl, DevLight* dl) {
     // mToWorld.rotateX(-PI / 2); rotateY(-PI / 2); setOrientation(orientation * mToWorld.getOrientation())
     Quat q = {1.0f, 0.0f, 0.0f, 0.0f};
     q = qnorm(qmul(axis_angle(0, -0.5f * kPi), q));
@@ -1291,6 +1291,12 @@ float pack_ibl_light(const gbl_scene_desc& d, const gbl_light& gl, const Aabb& s
     const Trs t = compose(kZero, qq, kOne);
     store3x4(t.m, dl->m);
     store3x4(t.inv, dl->inv);
+}
+// ... and what its texels decide: the image, the sampling distribution and the power
+float attach_ibl_texels(const gbl_scene_desc& d, const gbl_light& gl, const Aabb& scene_bound, PackedScene* out, DevLight* dl) {
+    out->extended = 1;
+    out->has_ibl = 1;
+    dl->image = gl.image;
     const IblTexels tx = {out->images[gl.image], d.texels};
     // mAverageRadiance = mRadiance->lookup(maxLevel, 0, 0): the bilinear lookup of the 1 x 1 level
     const uint32_t max_level = tx.im.levels - 1;
@@ -1307,37 +1313,29 @@ float pack_ibl_light(const gbl_scene_desc& d, const gbl_light& gl, const Aabb& s
     return power_of(avg, kPi, 4.0f * kPi * radius * radius);
 }
 
-// One function per kind of light, each returning the light's power; then the power distribution (Scene ctor, CDF1D::init)
+// Per light: the part the scene's geometry decides (emitting triangles, texels, the Whitted quota), then pack_light for the part
+// its gbl_light decides, which returns the light's power; then the power distribution
 void pack_lights(const gbl_scene_desc& d, const Aabb& scene_bound, PackedScene* out) {
     out->lights.resize(d.num_lights);
     out->light_tris.clear();
-    std::vector<float> power(d.num_lights);
+    out->light_power.assign(d.num_lights, 0.0f);
+    for (int k = 0; k < 3; ++k) out->bound_lo[k] = scene_bound.lo[k], out->bound_hi[k] = scene_bound.hi[k];
     for (uint32_t i = 0; i < d.num_lights; ++i) {
         const gbl_light& gl = d.lights[i];
         DevLight& dl = out->lights[i];
         memset(&dl, 0, sizeof(dl));
-        dl.type = gl.type;
-        for (int k = 0; k < 3; ++k) dl.color[k] = gl.color[k], dl.pos[k] = gl.position[k];
-        dl.cos_max = gl.cos_theta_max, dl.cos_falloff = gl.cos_falloff_start;
-        switch (gl.type) {
-            case GBL_LIGHT_SPOT:
-            case GBL_LIGHT_DIRECTIONAL: power[i] = pack_aimed_light(gl, scene_bound, out, &dl); break;
-            case GBL_LIGHT_AREA: power[i] = pack_area_light(d, gl, out, &dl); break;
-            case GBL_LIGHT_IBL: power[i] = pack_ibl_light(d, gl, scene_bound, out, &dl); break;
-            default: power[i] = power_of(dl.color, 4.0f * kPi); break;   // GBL_LIGHT_POINT
-        }
+        float texel_power = 0.0f;
+        if (gl.type == GBL_LIGHT_DIRECTIONAL) out->extended = 1;
+        if (gl.type == GBL_LIGHT_AREA) attach_area_geometry(d, gl, out, &dl);
+        if (gl.type == GBL_LIGHT_IBL) texel_power = attach_ibl_texels(d, gl, scene_bound, out, &dl);
         // WhittedRenderer::querySampleQuota: LightSampleIndex(quota, getSamplesNum()) -> roundToSquare slots
         const int root = static_cast<int>(std::ceil(std::sqrt(static_cast<float>(gl.sample_num))));
         dl.wh_n = static_cast<uint32_t>(root * root);
         dl.wh_prefix = static_cast<uint32_t>(out->wh_slots);
         out->wh_slots += static_cast<int32_t>(dl.wh_n);
+        out->light_power[i] = pack_light(gl, out->bound_lo, out->bound_hi, texel_power, &dl);
     }
-    out->light_cdf.assign(1, 0.0f);
-    out->light_pick_pdf.assign(std::max<uint32_t>(1, d.num_lights), 0.0f);
-    if (d.num_lights == 0) return;
-    const float integral = cdf1d(power.data(), power.size(), &out->light_cdf);
-    const float dx = 1.0f / d.num_lights;
-    for (uint32_t i = 0; i < d.num_lights; ++i) out->light_pick_pdf[i] = (power[i] / integral) * dx;
+    pack_light_distribution(out->light_power, &out->light_cdf, &out->light_pick_pdf);
 }
 
 // ------------------------------------------------------ medium, film, hot prefix
@@ -1451,6 +1449,38 @@ void hot_prefix(const gbl_scene_desc& d, PackedScene* out) {
 }
 
 }  // namespace
+
+// One statement of each light's packing: pack_scene's and gbl_update_lights'
+float pack_light(const gbl_light& gl, const float bound_lo[3], const float bound_hi[3], float kept_power, DevLight* dl) {
+    dl->type = gl.type;
+    for (int k = 0; k < 3; ++k) dl->color[k] = gl.color[k], dl->pos[k] = gl.position[k];
+    dl->cos_max = gl.cos_theta_max, dl->cos_falloff = gl.cos_falloff_start;
+    Aabb scene_bound;
+    for (int k = 0; k < 3; ++k) scene_bound.lo[k] = bound_lo[k], scene_bound.hi[k] = bound_hi[k];
+    switch (gl.type) {
+        case GBL_LIGHT_SPOT:
+        case GBL_LIGHT_DIRECTIONAL: return pack_aimed_light(gl, scene_bound, dl);
+        case GBL_LIGHT_AREA: return pack_area_light(gl, dl);
+        case GBL_LIGHT_IBL: pack_ibl_rotation(gl, dl); return kept_power;
+        default: return power_of(dl->color, 4.0f * kPi);   // GBL_LIGHT_POINT
+    }
+}
+
+void pack_light_distribution(const std::vector<float>& power, std::vector<float>* cdf, std::vector<float>* pick_pdf) {
+    const uint32_t n = static_cast<uint32_t>(power.size());
+    cdf->assign(1, 0.0f);
+    pick_pdf->assign(std::max<uint32_t>(1, n), 0.0f);
+    if (n == 0) return;
+    const float integral = cdf1d(power.data(), power.size(), cdf);
+    const float dx = 1.0f / n;
+    for (uint32_t i = 0; i < n; ++i) (*pick_pdf)[i] = (power[i] / integral) * dx;
+}
+
+void repack_lights(const gbl_light* edited, uint32_t first, uint32_t count, const float bound_lo[3], const float bound_hi[3], std::vector<DevLight>* lights,
+                   std::vector<float>* power, std::vector<float>* cdf, std::vector<float>* pick_pdf) {
+    for (uint32_t i = 0; i < count; ++i) (*power)[first + i] = pack_light(edited[i], bound_lo, bound_hi, (*power)[first + i], &(*lights)[first + i]);
+    pack_light_distribution(*power, cdf, pick_pdf);
+}
 
 // Validate, then pack: every refusal comes from validate_desc, before any table is built; of the packers only the TLAS step
 // returns a status (build_tlas keeps its check for gbl_update_instances) and after validation it cannot fail.

@@ -25,6 +25,8 @@ struct PackedScene {
     std::vector<DevLight> lights;
     std::vector<DevLightTri> light_tris;
     std::vector<float> light_cdf, light_pick_pdf;
+    std::vector<float> light_power;       // per light: what light_cdf and light_pick_pdf are made of (pack_light_distribution)
+    float bound_lo[3], bound_hi[3];       // the scene bound the lights and the medium were packed with
     float filter_table[256];
     int32_t tlas_root = 0;
     int32_t stack_entries = 0;
@@ -85,6 +87,20 @@ void build_tlas_nodes(const DevInstanceBound* bounds, uint32_t count, int32_t tl
 // The 3x4 rows of a transform and of its inverse as build_tlas composes them for DevInstance::m / inv (gbl_render_motion's
 // previous transforms).  false, *err set to build_tlas's refusal for instance i, when the reference cannot invert it.
 bool pack_transform(const gbl_trs& to_world, uint32_t i, float m[12], float inv[12], std::string* err);
+
+// The part of a light's record that its gbl_light and the scene bound decide -- type, colour, position, cone, axis, m / inv --
+// and the light's power: what pack_scene writes per light and gbl_update_lights writes again.  `dl` arrives with the part the
+// scene's geometry decides already in place (pack_scene attaches it; an edit keeps it): tri_first, tri_count, sum_area, shape,
+// radius, wh_n, wh_prefix, image, dist_*.  An image based light's power is that of its texels over the scene bound, neither of
+// which an edit can change: `kept_power` is returned for it (pack_scene passes what it has just worked out).
+float pack_light(const gbl_light& gl, const float bound_lo[3], const float bound_hi[3], float kept_power, DevLight* dl);
+// The power distribution over the lights (Scene ctor, CDF1D::init): cdf gets power.size() + 1 floats, pick_pdf
+// max(1, power.size()).
+void pack_light_distribution(const std::vector<float>& power, std::vector<float>* cdf, std::vector<float>* pick_pdf);
+// Both over a context's tables: lights [first, first + count) replaced by `edited`, their records and powers packed again,
+// then the distribution.  The other lights' records and powers stay as they are.
+void repack_lights(const gbl_light* edited, uint32_t first, uint32_t count, const float bound_lo[3], const float bound_hi[3], std::vector<DevLight>* lights,
+                   std::vector<float>* power, std::vector<float>* cdf, std::vector<float>* pick_pdf);
 
 // One mesh's DevTriOrder records (the reference's visiting order, per mesh-local triangle number) and its object bound (the
 // bound of ALL its vertices), as pack_scene makes them: gbl_update_vertices makes them again over edited positions.

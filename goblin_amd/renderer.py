@@ -302,6 +302,62 @@ class HipPathTracer:
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
 
+    _LIGHT = np.dtype([("type", "<u4"), ("color", "<f4", 3), ("pos", "<f4", 3), ("cos_max", "<f4"), ("axis", "<f4", 3), ("cos_falloff", "<f4"),
+                       ("m", "<f4", 12), ("inv", "<f4", 12), ("tri_first", "<u4"), ("tri_count", "<u4"), ("sum_area", "<f4"), ("shape", "<u4"),
+                       ("radius", "<f4"), ("wh_n", "<u4"), ("wh_prefix", "<u4"), ("image", "<i4"), ("dist_offset", "<u4"), ("dist_w", "<u4"),
+                       ("dist_h", "<u4"), ("pad", "<f4")])
+
+    def lights(self):
+        """The light records the context holds now (gbl_get_lights): a list of gbl_light, the scene's at first, the edited ones
+        after ``update_lights``."""
+        n = int(self.scene.desc.num_lights)
+        arr = (_abi.gbl_light * max(n, 1))()
+        st = self.lib.gbl_get_lights(self.handle, 0, n, arr)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, "gbl_get_lights")
+        return [arr[i] for i in range(n)]
+
+    def update_lights(self, first, lights=None, stream=None, **fields):
+        """Edit lights (gbl_update_lights).  ``lights``: gbl_light records for lights first..; without it, light ``first`` takes
+        the named gbl_light fields -- color, position, direction (3 floats each), cos_theta_max, cos_falloff_start, to_world (a
+        (position, orientation wxyz, scale) tuple or a gbl_trs) -- and what is not given keeps its value.  type, mesh, sample_num
+        and image cannot change.  Queued on ``stream`` (a torch stream; the current one by default) without a synchronisation,
+        unless an area light moves: its instances move with it, which synchronises the device as ``update_instances`` does."""
+        torch = _torch()
+        if lights is None:
+            light = self.lights()[first] if fields else None
+            names = {name for name, _ in _abi.gbl_light._fields_}
+            for name, value in fields.items():
+                if name not in names:
+                    raise TypeError("gbl_light has no field %r" % name)
+                if name == "to_world" and not isinstance(value, _abi.gbl_trs):
+                    for part, values in zip(("position", "orientation", "scale"), value):
+                        getattr(light.to_world, part)[:] = [float(v) for v in values]
+                elif isinstance(getattr(light, name), C.Array):
+                    getattr(light, name)[:] = [float(v) for v in value]
+                else:
+                    setattr(light, name, value)
+            lights = [light] if fields else []
+        arr = (_abi.gbl_light * max(len(lights), 1))(*lights)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        st = self.lib.gbl_update_lights(self.handle, int(first), len(lights), arr, s.cuda_stream)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        self.lib.gbl_get_info(self.handle, C.byref(self.info))   # (a moved area light rebuilds the TLAS)
+
+    def _lights_raw(self):
+        """The device's light records, light_cdf and light_pick_pdf read back (gbl_selftest_lights): a dict of records (a numpy
+        structured array), cdf, pick_pdf and total.  For tests."""
+        total = C.c_uint64()
+        st = self.lib.gbl_selftest_lights(self.handle, None, None, None, C.byref(total))
+        if st == _abi.GBL_OK:
+            n = total.value
+            records, cdf, pick = np.zeros(n, self._LIGHT), np.zeros(n + 1, np.float32), np.zeros(max(n, 1), np.float32)
+            st = self.lib.gbl_selftest_lights(self.handle, records.ctypes.data, cdf.ctypes.data, pick.ctypes.data, None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return {"records": records, "cdf": cdf, "pick_pdf": pick, "total": n}
+
     def _query_flags(self, kind, exact_ties, normals):
         if kind not in ("closest", "any"):
             raise ValueError("kind must be 'closest' or 'any', got %r" % (kind,))

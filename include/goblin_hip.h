@@ -884,6 +884,46 @@ gbl_status gbl_selftest_geometry(gbl_ctx* ctx, int table, uint64_t first, uint64
 gbl_status gbl_update_camera(gbl_ctx* ctx, const gbl_camera* camera);
 gbl_status gbl_get_camera(const gbl_ctx* ctx, gbl_camera* out);
 
+/* Light edit: lights [first, first + count) take the given records (host memory).  After GBL_OK the light records, the light
+ * pick CDF and the pick probabilities on the device are byte for byte what gbl_create builds from the context's current
+ * description with those lights replaced, and every render, AOV pass and query queued afterwards equals the same call on such a
+ * fresh context, bit for bit.
+ *  - What may change, by type.  Point: color, position.  Spot: color, position, direction, cos_theta_max, cos_falloff_start.
+ *    Directional: color, direction (its power is taken over the scene bound the context was created with; every edit that could
+ *    change that bound is refused in a scene with such a light).  Area: color, to_world.  Image based: to_world.orientation (the
+ *    constructor's pre-rotation is applied as gbl_create applies it; the sampling distribution and the average radiance stay).
+ *  - What may not: type, mesh, sample_num and image fix the Whitted quota, the stream sampler's layout, the choice of kernels
+ *    and the emitting triangles, and must equal the context's values (gbl_get_lights returns them).
+ *  - An edit that moves no instance packs the three tables on the host and queues their uploads on `stream` (a hipStream_t, NULL
+ *    for the null stream) from pinned staging the context owns.  No kernel is launched and the device is not synchronised: work
+ *    queued on that stream before the call keeps the old lights, work queued after it sees the new ones.  A caller who renders
+ *    on another stream orders the two itself.  The staging has four slots; a fifth edit waits for the first one's upload.
+ *  - A changed to_world on an area light also moves every instance whose area_light names it, through gbl_update_instances' own
+ *    path: records, bounds, the TLAS rebuilt on the host (with gbl_update_instances' limit on the hot prefix), gbl_info.  This
+ *    synchronises the device, as gbl_update_instances does, and gbl_get_instances reports the new transform afterwards, so
+ *    gbl_render_motion carries the moved emitter like any other instance.  It is accepted only while each of those instances'
+ *    transforms is bitwise the light's (a scene file's emissive model is loaded that way, and stays that way after an edit).
+ *    gbl_update_instances on such an instance stays refused.
+ *  - GBL_SCHEDULE_AUTO measures its rays per path again.
+ * Refusals, in this order, nothing uploaded and the context untouched: GBL_ERR_INVALID for a NULL ctx or lights; GBL_ERR_INVALID
+ * for a range past the context's lights; per light of the range GBL_ERR_INVALID for a type, mesh, sample_num or image that is
+ * not the context's, naming the light and the field, and GBL_ERR_UNSUPPORTED for a different color on an image based light
+ * (it is baked into the texels when the scene is loaded); per light GBL_ERR_INVALID for a float that is not finite in a field
+ * the light's type may change, and for a spot or directional direction of (0, 0, 0); then for a moved area light
+ * GBL_ERR_UNSUPPORTED in a scene with a directional or image based light (gbl_update_instances' refusal, with this entry's
+ * name), GBL_ERR_UNSUPPORTED for a carrying instance whose transform is not the light's, and GBL_ERR_INVALID for a transform
+ * the reference cannot invert (gbl_update_instances' |det| < 1e-5 refusal).  Every other value gbl_create accepts is accepted,
+ * a light without power among them.  count == 0 with a valid pointer is GBL_OK and changes nothing. */
+gbl_status gbl_update_lights(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_light* lights /* host */, void* stream);
+/* The light records the context holds now for lights [first, first + count): gbl_create's at first, the edited ones after
+ * gbl_update_lights.  Host only.  GBL_ERR_INVALID for a NULL argument or a range out of bounds. */
+gbl_status gbl_get_lights(const gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_light* out /* host */);
+/* Self-test hook: every DevLight record (192 B: type, color[3], pos[3], cos_max, axis[3], cos_falloff, m[12], inv[12], tri_first,
+ * tri_count, sum_area, shape, radius, wh_n, wh_prefix, image, dist_offset, dist_w, dist_h, pad), the lights + 1 floats of the
+ * pick CDF and the max(1, lights) pick probabilities to host memory, and *total (the light count).  Any out pointer may be NULL.
+ * Synchronises the device when it copies. */
+gbl_status gbl_selftest_lights(gbl_ctx* ctx, void* records_out, float* cdf_out, float* pick_pdf_out, uint64_t* total);
+
 /* Scene queries: Scene::intersect (GBL_QUERY_CLOSEST) or Scene::occluded (GBL_QUERY_ANY) for n caller rays in DEVICE memory,
  * against the context as it is now -- every gbl_update_instances*, gbl_update_vertices*, gbl_rebuild_mesh edit taken so far is
  * seen.  What a simulation step on the GPU asks between two edits: collision probes, ground snapping, line of sight, picking,
