@@ -675,10 +675,61 @@ __device__ __forceinline__ float4 wf_apply_medium(const RenderArgs& ra, float4 L
 // The sums take the same addends in the same order as ImageTile::addSample's cells did before: same samples per (wave, lane),
 // same 25-cell order, same atomics.  Measured and not kept (DESIGN_HISTORY, "SLP pairing off ..."): the 25 cells as straight-line
 // code with a select on each sum, and the radiance staged through LDS with coalesced loads.
-template <bool REPLAY, bool STATS, bool POW2>
+//
+// The windowed variants.  A half-width-2 filter touches 4 x 4 of the 25 cells unless the sample sits on a pixel centre line, and
+// all lanes of a wave filter the same sample index at the same time: under the native law sample k sits in sub-cell
+// (k % root, k / root) of its pixel, so which four columns and which four rows are touched is the same for every lane (up to
+// the rounding of px + u at a sub-cell boundary).  Per sample the lanes compare their window (start and count per axis, from
+// the same cx0 .. cy1 as before) with the first live lane's; when all agree on starts in {0, 1} and counts of 4 a scalar branch
+// picks wf_splat_window<.., SX, SY>, straight-line code for those 16 cells only.  Anything else -- a lane that disagrees, a count
+// of 5 (a sample on a centre line) or below 4 (narrower filters), an odd root's middle sub-cell, the stream sampler's positions
+// where they differ between lanes, a NaN sample in the wave -- takes the 25-cell body, wave-uniformly.  A lane's 25 sums are bit
+// for bit what the 25-cell body alone gives: each sum receives the same addend of the same samples in the same order, from the
+// same expressions; the cells left out are the ones whose branch the lane did not take (the 25-cell body already skipped them
+// behind s_cbranch_execz: what a variant saves is their compares and mask pairs, the fifth column's and row's bins, nine table
+// reads and the range tests).  The film therefore differs from the 25-cell body's only as two runs of one binary differ (float
+// atomics).
+// INSIDE (per workgroup): all 25 footprint pixels of every pixel of the tile are inside the film's crop, so the 16 updates are
+// unconditional, with no exec-mask pair; otherwise they keep the lane's crop predicates.
+// The wave's index is read as a scalar, so the loop over its samples, the sample's sub-cell (two integer divisions) and the
+// prefetch address are the scalar unit's.
+template <bool STATS, bool POW2, bool INSIDE, int SX, int SY>
+__device__ __forceinline__ void wf_splat_window(const float* ftab, float (&acc)[25][4], const float (&fx)[5], const float (&fy)[5], const bool (&inx)[5],
+                                                const bool (&iny)[5], float dx, float dy, float rx, float ry, const float4& L, LaneCounters& cnt) {
+    int ix[4], row[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const float tx = 16 * (fx[SX + o] - dx), ty = 16 * (fy[SY + o] - dy);
+        ix[o] = min(static_cast<int>(floorf(fabsf(POW2 ? tx * rx : tx / rx))), 15);
+        row[o] = 16 * min(static_cast<int>(floorf(fabsf(POW2 ? ty * ry : ty / ry))), 15);
+    }
+#pragma unroll
+    for (int oy = 0; oy < 4; ++oy) {
+        float w[4];
+#pragma unroll
+        for (int ox = 0; ox < 4; ++ox) w[ox] = ftab[row[oy] + ix[ox]];
+#pragma unroll
+        for (int ox = 0; ox < 4; ++ox) {
+            if (INSIDE || (inx[SX + ox] && iny[SY + oy])) {
+                float* a = acc[(SY + oy) * 5 + SX + ox];
+                a[0] += w[ox] * L.x;
+                a[1] += w[ox] * L.y;
+                a[2] += w[ox] * L.z;
+                a[3] += w[ox];
+                if (STATS) cnt.splats += 1;
+            }
+        }
+    }
+}
+
+// a wave-uniform condition as a scalar word the optimiser does not see through
+__device__ __forceinline__ int wf_scalar_flag(bool uniform) { return __builtin_amdgcn_readfirstlane(uniform ? 1 : 0); }
+
+template <bool REPLAY, bool STATS, bool POW2, bool INSIDE>
 __device__ __forceinline__ void wf_splat_fast5(const DevScene& sc, const RenderArgs& ra, const WfArgs& wa, const float* ftab, float* tile, int tp,
                                                int tx0, int ty0, int px, int py, LaneCounters& cnt) {
-    const int wave = threadIdx.x >> 6;
+    // (the wave's index as a scalar: the loop over its samples, the sample's sub-cell and the window's branch are the scalar unit's)
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     SampleSource src = camera_source<false>(sc, ra, px, py, 0u, nullptr);   // (the native law's; src.k per sample)
     const uint32_t local_pixel = window_pixel(ra, px, py);
     float acc[25][4];
@@ -698,7 +749,14 @@ __device__ __forceinline__ void wf_splat_fast5(const DevScene& sc, const RenderA
         inx[o] = x >= xlo && x <= xhi;
         iny[o] = y >= ylo && y <= yhi;
     }
+    // the radiance of the wave's next sample is asked for ahead of this sample's cells (the last one asks for itself again and
+    // leaves the value unused)
+    const float4* li = wa.li_buf + static_cast<size_t>(local_pixel) * wa.pass_spp;
+    float4 L_next = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (wave < wa.pass_spp) L_next = li[wave];
     for (int kk = wave; kk < wa.pass_spp; kk += GBL_BLOCK / 64) {
+        const float4 L_raw = L_next;
+        L_next = li[min(kk + GBL_BLOCK / 64, wa.pass_spp - 1)];
         src.k = static_cast<uint32_t>(wa.pass_k0 + kk);
         float image_x, image_y;
         if (REPLAY) {
@@ -708,12 +766,33 @@ __device__ __forceinline__ void wf_splat_fast5(const DevScene& sc, const RenderA
         } else {
             image_position<false>(src, px, py, &image_x, &image_y);
         }
-        const float4 L = wf_apply_medium(ra, wa.li_buf[static_cast<size_t>(local_pixel) * wa.pass_spp + kk],
-                                         static_cast<size_t>(local_pixel) * ra.spp + src.k);
-        if (L.x != L.x || L.y != L.y || L.z != L.z) continue;   // NaN sample: dropped
+        const float4 L = wf_apply_medium(ra, L_raw, static_cast<size_t>(local_pixel) * ra.spp + src.k);
+        const bool nan = L.x != L.x || L.y != L.y || L.z != L.z;   // NaN sample: dropped
         const float dx = image_x - 0.5f, dy = image_y - 0.5f;
         const int cx0 = static_cast<int>(ceilf(dx - wx)), cx1 = static_cast<int>(floorf(dx + wx));
         const int cy0 = static_cast<int>(ceilf(dy - wy)), cy1 = static_cast<int>(floorf(dy + wy));
+        // the wave's valid lanes vote.  A lane's word: 1 + column start + 2 * row start for a 4 x 4 window that starts at column 0 or
+        // 1 and row 0 or 1 of its 5x5 block, 0 for any other window and for a NaN sample
+        const int sx = cx0 - (px - 2), sy = cy0 - (py - 2);
+        const bool fits = !nan && static_cast<uint32_t>(sx | sy) <= 1u && cx1 - cx0 == 3 && cy1 - cy0 == 3;
+        const int code = fits ? 1 + sx + 2 * sy : 0;
+        const int code0 = __builtin_amdgcn_readfirstlane(code);
+        // the word all agree on (0: none, the 25-cell body), and from it four scalar flags, at most one set; each guards its variant
+        // on its own.  (One opaque flag per branch keeps them four plain conditional blocks that update the sums in place: as one
+        // switch the structuriser's flow blocks carried a second copy of the 100 sums, 250 VGPRs.)
+        const int agreed = __builtin_amdgcn_readfirstlane(__ballot(code != code0) == 0ull ? code0 : 0);
+#define GBL_SPLAT_PICK(SX, SY) (wf_scalar_flag(agreed == 1 + SX + 2 * SY) != 0)
+#define GBL_SPLAT_WINDOW(SX, SY) \
+    wf_splat_window<STATS, POW2, INSIDE, SX, SY>(ftab, acc, fx, fy, inx, iny, dx, dy, rx, ry, L, cnt)
+        const bool w00 = GBL_SPLAT_PICK(0, 0), w10 = GBL_SPLAT_PICK(1, 0), w01 = GBL_SPLAT_PICK(0, 1), w11 = GBL_SPLAT_PICK(1, 1);
+        if (w00) GBL_SPLAT_WINDOW(0, 0);
+        if (w10) GBL_SPLAT_WINDOW(1, 0);
+        if (w01) GBL_SPLAT_WINDOW(0, 1);
+        if (w11) GBL_SPLAT_WINDOW(1, 1);
+#undef GBL_SPLAT_WINDOW
+#undef GBL_SPLAT_PICK
+        if (nan || w00 || w10 || w01 || w11) continue;
+        // the 25-cell body: every other sample
         int ix[5], row[5];
         bool onx[5], ony[5];
 #pragma unroll
@@ -766,8 +845,9 @@ __device__ __forceinline__ bool wf_power_of_two(float w) {   // a normal float w
     return (u & 0x807fffffu) == 0u && (u >> 23) != 0u && (u >> 23) != 255u;
 }
 
+// (three waves per SIMD, as before: without the bound the allocator takes 169 VGPRs, one above that step; four spill)
 template <bool REPLAY, bool STATS>
-__global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra, WfArgs wa) {
+__global__ __launch_bounds__(GBL_BLOCK, 3) void wf_splat(DevScene sc, RenderArgs ra, WfArgs wa) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tp = GBL_TILE + 2 * sc.film.halo;
     float* tile = reinterpret_cast<float*>(smem);
@@ -791,10 +871,19 @@ __global__ __launch_bounds__(GBL_BLOCK) void wf_splat(DevScene sc, RenderArgs ra
     const bool fast5 = (!REPLAY || ra.image_xy != nullptr) && sc.film.wx <= 2.0f && sc.film.wy <= 2.0f;
     const bool valid = px < ra.window[1] && py < ra.window[3];
     if (valid && fast5) {
-        if (wf_power_of_two(sc.film.wx) && wf_power_of_two(sc.film.wy))   // (uniform over the launch)
-            wf_splat_fast5<REPLAY, STATS, true>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
-        else
-            wf_splat_fast5<REPLAY, STATS, false>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+        // (per workgroup) the 5x5 blocks of all 64 pixels of the tile lie inside the film's crop: no lane's crop predicate can fail
+        const bool inside = px0 - 2 >= sc.film.xstart && px0 + GBL_TILE + 1 <= sc.film.xstart + sc.film.xcount - 1 &&
+                            py0 - 2 >= sc.film.ystart && py0 + GBL_TILE + 1 <= sc.film.ystart + sc.film.ycount - 1;
+        if (wf_power_of_two(sc.film.wx) && wf_power_of_two(sc.film.wy)) {   // (uniform over the launch)
+            if (inside)
+                wf_splat_fast5<REPLAY, STATS, true, true>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+            else
+                wf_splat_fast5<REPLAY, STATS, true, false>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+        } else if (inside) {
+            wf_splat_fast5<REPLAY, STATS, false, true>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+        } else {
+            wf_splat_fast5<REPLAY, STATS, false, false>(sc, ra, wa, ftab, tile, tp, tx0, ty0, px, py, cnt);
+        }
     } else if (valid) {
         SampleSource src = camera_source<false>(sc, ra, px, py, 0u, nullptr);   // (the native law's; src.k and src.rec per sample)
         const uint32_t local_pixel = window_pixel(ra, px, py);
