@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -89,11 +88,8 @@ gbl_status ensure_plan(gbl_ctx* ctx, uint32_t mesh) {
 // Forget the mesh's refit plan (its tree is about to be replaced): the next edit, or gbl_mesh_tree_stats, makes it again
 void drop_plan(gbl_ctx* ctx, uint32_t mesh) {
     gbl_ctx::MeshRefit& mr = ctx->refit[mesh];
-    for (void* p : {static_cast<void*>(mr.plan), static_cast<void*>(mr.node_box)}) {
-        if (!p) continue;
-        ctx->allocations.erase(std::remove(ctx->allocations.begin(), ctx->allocations.end(), p), ctx->allocations.end());
-        (void)hipFree(p);
-    }
+    device_free(ctx, mr.plan);
+    device_free(ctx, mr.node_box);
     mr = gbl_ctx::MeshRefit();
 }
 
@@ -109,8 +105,7 @@ gbl_status grow_nodes(gbl_ctx* ctx, uint32_t extra, int32_t* first_new) {
     if (old_n > 0) HIP_TRY(ctx, hipMemcpy(grown, old, old_n * sizeof(DevNode), hipMemcpyDeviceToDevice));
     HIP_TRY(ctx, hipMemset(static_cast<DevNode*>(grown) + old_n, 0, extra * sizeof(DevNode)));
     HIP_TRY(ctx, hipDeviceSynchronize());
-    ctx->allocations.erase(std::remove(ctx->allocations.begin(), ctx->allocations.end(), static_cast<void*>(old)), ctx->allocations.end());
-    (void)hipFree(old);
+    device_free(ctx, old);
     ctx->scene.nodes = static_cast<const DevNode*>(grown);
     ctx->num_nodes = new_n;
     ctx->info.scene_bytes += static_cast<uint64_t>(extra) * sizeof(DevNode);
@@ -138,10 +133,7 @@ gbl_status check_edit_allowed(gbl_ctx* ctx, uint32_t mesh, bool normals) {
     if (ctx->mesh_emits[mesh])
         return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_vertices: mesh " + std::to_string(mesh) + " is the geometry of an area light, whose emitting "
                                               "triangles, area distribution and power would have to follow; re-create the context instead");
-    if (ctx->has_directional)
-        return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_vertices: a directional or image based light's power (and the image based light's sampling sphere) "
-                                              "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead");
-    return GBL_OK;
+    return refuse_scene_bound_edit(ctx, "gbl_update_vertices");
 }
 
 // The refit launches over the mesh's positions as the device holds them: triangles and their bounds, then the nodes from the
@@ -179,9 +171,7 @@ gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first,
     for (size_t i = 0; i < 3 * static_cast<size_t>(count); ++i)
         if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i]))) return fail_not_finite(ctx, first, i, !std::isfinite(positions[i]));
     if ((st = check_edit_allowed(ctx, mesh, normals != nullptr)) != GBL_OK) return st;
-    const auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
+    LapClock clock;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables
     if ((st = ensure_plan(ctx, mesh)) != GBL_OK) return st;
@@ -196,21 +186,17 @@ gbl_status gbl_update_vertices_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t first,
     }
     launch_refit(ctx, mesh);
     HIP_TRY(ctx, hipGetLastError());
-    const auto t1 = now();
+    const double launch_ms = clock.lap_ms();
     // while the device works: the reference's visiting order over the edited positions (what exact_ties, replay, stream and the
     // EXT builds break ties by), and the mesh's object bound
     if ((st = make_order(ctx, mesh)) != GBL_OK) return st;
-    const auto t2 = now();
+    const double order_ms = clock.lap_ms();
     mesh_object_bound(ctx->h_positions.data() + 3 * static_cast<size_t>(gm.vertex_offset), gm.vertex_count, &ctx->mesh_lo[3 * mesh], &ctx->mesh_hi[3 * mesh]);
-    if ((st = refresh_instance_mirror(ctx)) != GBL_OK) return st;   // (a device instance edit may have left the transforms' host copy behind)
-    std::vector<gbl_instance> instances = ctx->h_instances;
-    st = rebuild_tlas(ctx, instances, "gbl_update_vertices");   // (synchronises before its uploads, and clears the AUTO pilot)
-    if (st != GBL_OK) return st;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (getenv("GBL_PROBE"))
+    if ((st = retlas_after_geometry_edit(ctx, "gbl_update_vertices")) != GBL_OK) return st;
+    if (probing())
         fprintf(stderr, "probe: gbl_update_vertices mesh %u (%u triangles, %zu refit levels): synchronise, plan, uploads and launches %.3f ms, tri_order on the host and "
                         "its upload (behind the kernels) %.3f ms, mesh bound and TLAS %.3f ms\n", mesh, gm.tri_count, mr.level_first.empty() ? size_t(0) : mr.level_first.size() - 1,
-                ms(t0, t1), ms(t1, t2), ms(t2, now()));
+                launch_ms, order_ms, clock.lap_ms());
     return GBL_OK;
 }
 
@@ -230,9 +216,7 @@ gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((st = check_device_pointer(ctx, d_positions, floats * sizeof(float), "gbl_update_vertices_device", "d_positions")) != GBL_OK) return st;
     if (d_normals && (st = check_device_pointer(ctx, d_normals, floats * sizeof(float), "gbl_update_vertices_device", "d_normals")) != GBL_OK) return st;
-    const auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
+    LapClock clock;
     if (!ctx->vertex_words.p && (st = grow(ctx, ctx->vertex_words, GBL_VW_BYTES, "vertex edit words")) != GBL_OK) return st;
     unsigned char* words = static_cast<unsigned char*>(ctx->vertex_words.p);
     HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables, and whatever wrote the caller's floats is done
@@ -249,7 +233,7 @@ gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t
             return fail_not_finite(ctx, first, bad, !std::isfinite(v));
         }
     }
-    const auto t1 = now();
+    const double check_ms = clock.lap_ms();
     if ((st = ensure_plan(ctx, mesh)) != GBL_OK) return st;
     DevScene& sc = ctx->scene;
     const size_t m0 = 3 * static_cast<size_t>(gm.vertex_offset), v0 = m0 + 3 * static_cast<size_t>(first);
@@ -263,7 +247,7 @@ gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t
     launch_refit(ctx, mesh);
     gbl_launch_mesh_bound(sc.positions + m0, gm.vertex_count, reinterpret_cast<unsigned long long*>(words + GBL_VW_KEYS), reinterpret_cast<float*>(words + GBL_VW_BOUND), 0);
     HIP_TRY(ctx, hipGetLastError());
-    const auto t2 = now();
+    const double launch_ms = clock.lap_ms();
     // the tie order: now, on the host over the refreshed mirror (while the device works), or left to its first reader
     if (flags & GBL_VERTICES_DEFER_ORDER) {
         if (!ctx->order_pending[mesh]) {
@@ -274,18 +258,14 @@ gbl_status gbl_update_vertices_device_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t
         if ((st = refresh_mirror(ctx, mesh)) != GBL_OK) return st;
         if ((st = make_order(ctx, mesh)) != GBL_OK) return st;
     }
-    const auto t3 = now();
+    const double order_ms = clock.lap_ms();
     float bound[6];
     HIP_TRY(ctx, hipMemcpy(bound, words + GBL_VW_BOUND, sizeof(bound), hipMemcpyDeviceToHost));
     for (int a = 0; a < 3; ++a) ctx->mesh_lo[3 * mesh + a] = bound[a], ctx->mesh_hi[3 * mesh + a] = bound[3 + a];
-    if ((st = refresh_instance_mirror(ctx)) != GBL_OK) return st;   // (a device instance edit may have left the transforms' host copy behind)
-    std::vector<gbl_instance> instances = ctx->h_instances;
-    st = rebuild_tlas(ctx, instances, "gbl_update_vertices_device");   // (synchronises before its uploads, and clears the AUTO pilot)
-    if (st != GBL_OK) return st;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (getenv("GBL_PROBE"))
+    if ((st = retlas_after_geometry_edit(ctx, "gbl_update_vertices_device")) != GBL_OK) return st;
+    if (probing())
         fprintf(stderr, "probe: gbl_update_vertices_device mesh %u (%u triangles, flags %u): synchronise, check and its word %.3f ms, plan, copies and launches %.3f ms, "
-                        "tri_order %.3f ms, bound read-back and TLAS %.3f ms\n", mesh, gm.tri_count, flags, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, now()));
+                        "tri_order %.3f ms, bound read-back and TLAS %.3f ms\n", mesh, gm.tri_count, flags, check_ms, launch_ms, order_ms, clock.lap_ms());
     return GBL_OK;
 }
 
@@ -313,9 +293,7 @@ gbl_status gbl_rebuild_mesh_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
     const gbl_mesh& gm = ctx->h_meshes[mesh];
     const uint32_t n = gm.tri_count, tri_first = ctx->mesh_tri_first[mesh];
     if (n == 0) return GBL_OK;
-    const auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
+    LapClock clock;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables
     // first rebuild of the mesh: its index slice goes up (a host-built context has none on the device), and a mesh with a tree
@@ -330,7 +308,7 @@ gbl_status gbl_rebuild_mesh_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
         if ((st = grow_nodes(ctx, n, &ctx->rebuild_slot[mesh])) != GBL_OK) return st;
         ctx->h_nodes.clear();
     }
-    const auto t1 = now();
+    const double slot_ms = clock.lap_ms();
     DevScene& sc = ctx->scene;
     int32_t root = 0;
     uint32_t used = 0;
@@ -340,7 +318,7 @@ gbl_status gbl_rebuild_mesh_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
                                (gm.has_normal ? 1u : 0u) | (gm.has_uv ? 2u : 0u), &root, &used, &depth);
     if (st != GBL_OK) return st;
     if (used > n) return fail(ctx, GBL_ERR_INTERNAL, "gbl_rebuild_mesh: the tree outgrew the mesh's node records");
-    const auto t2 = now();
+    const double build_ms = clock.lap_ms();
     gbl_launch_refit_tris(const_cast<DevTri*>(sc.tris), const_cast<DevTriBound*>(sc.tri_bounds), sc.tri_shade, sc.positions,
                           static_cast<uint32_t>(ctx->h_positions.size() / 3), tri_first, n, 0);
     HIP_TRY(ctx, hipGetLastError());
@@ -350,15 +328,11 @@ gbl_status gbl_rebuild_mesh_impl(gbl_ctx* ctx, uint32_t mesh, uint32_t flags) {
     ctx->mesh_stack_need[mesh] = 3 * depth;
     ctx->blas_depth = std::max(ctx->blas_depth, depth);
     ctx->info.blas_depth = ctx->blas_depth;   // (a bound from here on: the deepest tree any mesh of the context has had)
-    if ((st = refresh_instance_mirror(ctx)) != GBL_OK) return st;   // (a device instance edit may have left the transforms' host copy behind)
-    std::vector<gbl_instance> instances = ctx->h_instances;
-    st = rebuild_tlas(ctx, instances, "gbl_rebuild_mesh");   // (synchronises before its uploads, recomputes stack_entries, and clears the AUTO pilot)
-    if (st != GBL_OK) return st;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (getenv("GBL_PROBE"))
+    if ((st = retlas_after_geometry_edit(ctx, "gbl_rebuild_mesh")) != GBL_OK) return st;
+    if (probing())
         fprintf(stderr, "probe: gbl_rebuild_mesh mesh %u (%u triangles -> %u nodes, %d levels, slot %d): synchronise, indices and slot %.3f ms, build kernels "
-                        "(one read-back per level) %.3f ms, triangle bounds and TLAS %.3f ms\n", mesh, n, used, depth, ctx->rebuild_slot[mesh], ms(t0, t1), ms(t1, t2),
-                ms(t2, now()));
+                        "(one read-back per level) %.3f ms, triangle bounds and TLAS %.3f ms\n", mesh, n, used, depth, ctx->rebuild_slot[mesh], slot_ms, build_ms,
+                clock.lap_ms());
     return GBL_OK;
 }
 

@@ -1,12 +1,12 @@
-// libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): instance edits from device memory.
-// gbl_update_instances_device composes the edited instances' records on the device (kernels/instances.h) and builds the TLAS
-// on the host over the boxes read back, as every edit does, or -- GBL_INSTANCES_DEVICE_TLAS -- on the device with the linear
-// builder (kernels/lbvh.h).  gbl_get_instances_device and the self-test hook go with it, and the two helpers that keep the
-// host copy of the transforms (h_instances[i].to_world) and the device's raw table in step.
+// libgoblin_hip.so -- C ABI of the device integrator (include/goblin_hip.h): instance edits, and the TLAS every scene edit ends
+// in.  gbl_update_instances packs the edited list on the host (scene_prep.cpp build_tlas); its tail, move_instances, is the light
+// edits' and, moving nothing, the geometry edits' (gbl_host.h).  gbl_update_instances_device composes the edited instances'
+// records on the device (kernels/instances.h) and builds the TLAS on the host over the boxes read back, or --
+// GBL_INSTANCES_DEVICE_TLAS -- on the device with the linear builder (kernels/lbvh.h).  gbl_get_instances_device, the self-test
+// hook, and the two helpers that keep h_instances[i].to_world and the device's raw table in step go with it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,7 +37,80 @@ gbl_status write_instance_table(gbl_ctx* ctx, uint32_t first, uint32_t count) {
     return GBL_OK;
 }
 
+void commit_tlas(gbl_ctx* ctx, int32_t root, int depth, size_t nodes, int stack_entries) {
+    ctx->scene.tlas_root = root;
+    ctx->scene.stack_entries = stack_entries;   // (the wavefront stack backing is re-checked at render time)
+    ctx->info.tlas_depth = depth;
+    ctx->info.tlas_nodes = nodes;
+    ctx->auto_rays_per_path.clear();   // the edited scene's paths may be longer or shorter: AUTO measures again
+}
+
+gbl_status refuse_scene_bound_edit(gbl_ctx* ctx, const char* who) {
+    if (!ctx->has_directional) return GBL_OK;
+    return fail(ctx, GBL_ERR_UNSUPPORTED, std::string(who) + ": a directional or image based light's power (and the image based light's sampling sphere) "
+                                          "depends on the scene bound (GoblinLight.cpp:203-210, 590-629); re-create the context instead");
+}
+
+gbl_status move_instances(gbl_ctx* ctx, const uint32_t* which, uint32_t count, const gbl_trs* to_world, const char* who) {
+    gbl_status st = refresh_instance_mirror(ctx);   // (a device instance edit may have left the transforms' host copy behind)
+    if (st != GBL_OK) return st;
+    std::vector<gbl_instance> edited = ctx->h_instances;
+    for (uint32_t i = 0; i < count; ++i) edited[which[i]].to_world = to_world[i];
+    const TlasInput in = {edited.data(),       static_cast<uint32_t>(edited.size()), ctx->h_meshes.data(),  ctx->h_materials.data(),
+                          ctx->mesh_lo.data(), ctx->mesh_hi.data(),                  ctx->mesh_root.data(), ctx->tlas_base};
+    TlasResult built;
+    std::string err;
+    if ((st = build_tlas(in, &built, &err)) != GBL_OK) return fail(ctx, st, err);
+    const std::vector<DevInstance>& inst = built.instances;
+    const std::vector<DevNode>& tlas = built.nodes;
+    const std::vector<DevInstanceBound>& bounds = built.instance_bounds;
+    if (tlas.size() > ctx->tlas_capacity) return fail(ctx, GBL_ERR_DEVICE, std::string(who) + ": rebuilt TLAS does not fit its reserved nodes");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the old TLAS
+    DevScene& sc = ctx->scene;
+    if (!inst.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstance*>(sc.instances), inst.data(), inst.size() * sizeof(DevInstance), hipMemcpyHostToDevice));
+    if (!bounds.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevInstanceBound*>(sc.instance_bounds), bounds.data(), bounds.size() * sizeof(DevInstanceBound), hipMemcpyHostToDevice));
+    if (!tlas.empty())
+        HIP_TRY(ctx, hipMemcpy(const_cast<DevNode*>(sc.nodes) + ctx->tlas_base, tlas.data(), tlas.size() * sizeof(DevNode), hipMemcpyHostToDevice));
+    commit_tlas(ctx, built.root, built.depth, tlas.size(), scene_stack_entries(tlas, ctx->tlas_base, built.root, inst, ctx->mesh_stack_need));
+    ctx->h_instances.swap(edited);
+    for (uint32_t i = 0; i < count;) {   // the raw table, run by run
+        uint32_t end = i + 1;
+        while (end < count && which[end] == which[end - 1] + 1) ++end;
+        if ((st = write_instance_table(ctx, which[i], end - i)) != GBL_OK) return st;
+        i = end;
+    }
+    return GBL_OK;
+}
+
+gbl_status retlas_after_geometry_edit(gbl_ctx* ctx, const char* who) {
+    if (const gbl_status st = move_instances(ctx, nullptr, 0, nullptr, who); st != GBL_OK) return st;   // (moves none: the mesh bounds and roots are what changed)
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return GBL_OK;
+}
+
 namespace {
+
+// What both instance edits refuse before they look at a transform, in gbl_update_instances' order and words
+gbl_status check_instance_edit(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
+    if (!to_world || static_cast<uint64_t>(first) + count > ctx->h_instances.size()) return fail(ctx, GBL_ERR_INVALID, "gbl_update_instances: instance range out of bounds");
+    if (const gbl_status st = refuse_scene_bound_edit(ctx, "gbl_update_instances"); st != GBL_OK) return st;
+    for (uint32_t i = 0; i < count; ++i)
+        if (ctx->h_instances[first + i].area_light >= 0)
+            return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_instances: instance " + std::to_string(first + i) + " carries an area light, whose own transform would "
+                                                  "have to move with it; re-create the context instead");
+    return GBL_OK;
+}
+
+gbl_status gbl_update_instances_impl(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
+    if (!ctx) return GBL_ERR_INVALID;
+    if (const gbl_status st = check_instance_edit(ctx, first, count, to_world); st != GBL_OK) return st;
+    std::vector<uint32_t> which(count);
+    for (uint32_t i = 0; i < count; ++i) which[i] = first + i;
+    return move_instances(ctx, which.data(), count, to_world, "gbl_update_instances");
+}
 
 // The raw table, made from the host copy at its first use (no device edit can have come before it: the copy is current)
 gbl_status ensure_instance_table(gbl_ctx* ctx) {
@@ -114,20 +187,14 @@ gbl_status gbl_update_instances_device_impl(gbl_ctx* ctx, uint32_t first, uint32
     if (!d_to_world) return fail(ctx, GBL_ERR_INVALID, "gbl_update_instances_device: d_to_world is NULL");
     if (flags & ~GBL_INSTANCES_DEVICE_TLAS) return fail(ctx, GBL_ERR_INVALID, "gbl_update_instances_device: unknown bits in flags");
     const size_t n = ctx->h_instances.size();
-    if (static_cast<uint64_t>(first) + count > n) return fail(ctx, GBL_ERR_INVALID, "gbl_update_instances: instance range out of bounds");
-    if (gbl_status bound = refuse_scene_bound_edit(ctx, "gbl_update_instances"); bound != GBL_OK) return bound;
-    for (uint32_t i = 0; i < count; ++i)
-        if (ctx->h_instances[first + i].area_light >= 0)
-            return fail(ctx, GBL_ERR_UNSUPPORTED, "gbl_update_instances: instance " + std::to_string(first + i) + " carries an area light, whose own transform would "
-                                                  "have to move with it; re-create the context instead");
+    gbl_status st = check_instance_edit(ctx, first, count, d_to_world);
+    if (st != GBL_OK) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    gbl_status st = check_device_pointer(ctx, d_to_world, static_cast<uint64_t>(count) * sizeof(gbl_trs), "gbl_update_instances_device", "d_to_world");
+    st = check_device_pointer(ctx, d_to_world, static_cast<uint64_t>(count) * sizeof(gbl_trs), "gbl_update_instances_device", "d_to_world");
     if (st != GBL_OK) return st;
     if (count == 0) return GBL_OK;
     const bool device_tlas = (flags & GBL_INSTANCES_DEVICE_TLAS) != 0 && n >= 2;   // (fewer than two instances: there is no tree to build)
-    const auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = now();
+    LapClock clock;
     HIP_TRY(ctx, hipDeviceSynchronize());   // no render may be reading the tables, and whatever wrote the caller's floats is done
     if ((st = ensure_instance_table(ctx)) != GBL_OK) return st;
     if ((st = ensure_mesh_bounds(ctx)) != GBL_OK) return st;
@@ -149,7 +216,7 @@ gbl_status gbl_update_instances_device_impl(gbl_ctx* ctx, uint32_t first, uint32
     unsigned long long word = 0;
     HIP_TRY(ctx, hipMemcpy(&word, d_word, sizeof(word), hipMemcpyDeviceToHost));
     if (word != ~0ull) return refuse_word(ctx, word, first, count, d_to_world);
-    const auto t1 = now();
+    const double compose_ms = clock.lap_ms();
 
     // the TLAS over the boxes of all instances, the edited ones' from staging: nothing of the context is written before it stands
     std::vector<DevNode> tlas;
@@ -173,7 +240,7 @@ gbl_status gbl_update_instances_device_impl(gbl_ctx* ctx, uint32_t first, uint32
     }
     if (tlas.size() > ctx->tlas_capacity) return fail(ctx, GBL_ERR_DEVICE, "gbl_update_instances_device: rebuilt TLAS does not fit its reserved nodes");
     const int stack_entries = scene_stack_entries(tlas, ctx->tlas_base, root, need_instances(ctx), ctx->mesh_stack_need);
-    const auto t2 = now();
+    const double tlas_ms = clock.lap_ms();
 
     // commit: the device is idle, the copies are ordered by the null stream
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<DevInstance*>(sc.instances) + first, s_inst, static_cast<size_t>(count) * sizeof(DevInstance), hipMemcpyDeviceToDevice, 0));
@@ -186,22 +253,14 @@ gbl_status gbl_update_instances_device_impl(gbl_ctx* ctx, uint32_t first, uint32
         else HIP_TRY(ctx, hipMemcpy(dst, tlas.data(), tlas.size() * sizeof(DevNode), hipMemcpyHostToDevice));
     }
     HIP_TRY(ctx, hipDeviceSynchronize());
-    sc.tlas_root = root;
-    sc.stack_entries = stack_entries;   // (the wavefront stack backing is re-checked at render time)
-    ctx->info.tlas_depth = depth;
-    ctx->info.tlas_nodes = tlas.size();
-    ctx->auto_rays_per_path.clear();   // the edited scene's paths may be longer or shorter: AUTO measures again
-    if (ctx->trs_stale_end <= ctx->trs_stale_first) {
-        ctx->trs_stale_first = first;
-        ctx->trs_stale_end = first + count;
-    } else {
-        ctx->trs_stale_first = std::min(ctx->trs_stale_first, first);
-        ctx->trs_stale_end = std::max(ctx->trs_stale_end, first + count);
-    }
-    if (getenv("GBL_PROBE"))
+    commit_tlas(ctx, root, depth, tlas.size(), stack_entries);
+    const bool none_stale = ctx->trs_stale_end <= ctx->trs_stale_first;   // the host copy's stale range takes the edit in
+    ctx->trs_stale_first = none_stale ? first : std::min(ctx->trs_stale_first, first);
+    ctx->trs_stale_end = none_stale ? first + count : std::max(ctx->trs_stale_end, first + count);
+    if (probing())
         fprintf(stderr, "probe: gbl_update_instances_device %u of %zu instances (flags %u): synchronise, tables, compose and its word %.3f ms, TLAS on the %s (%zu nodes, "
-                        "%d levels, stack entries %d) %.3f ms, commit %.3f ms\n", count, n, flags, ms(t0, t1), device_tlas ? "device" : "host", tlas.size(), depth,
-                stack_entries, ms(t1, t2), ms(t2, now()));
+                        "%d levels, stack entries %d) %.3f ms, commit %.3f ms\n", count, n, flags, compose_ms, device_tlas ? "device" : "host", tlas.size(), depth,
+                stack_entries, tlas_ms, clock.lap_ms());
     return GBL_OK;
 }
 
@@ -241,6 +300,10 @@ gbl_status gbl_selftest_instances_impl(gbl_ctx* ctx, uint64_t first, uint64_t co
 }   // namespace
 
 extern "C" {
+
+gbl_status gbl_update_instances(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* to_world) {
+    return gbl_guard([&] { return gbl_update_instances_impl(ctx, first, count, to_world); }, [&](const std::string& what) { if (ctx) ctx->error = what; });
+}
 
 gbl_status gbl_update_instances_device(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_trs* d_to_world, uint32_t flags) {
     return gbl_guard([&] { return gbl_update_instances_device_impl(ctx, first, count, d_to_world, flags); }, [&](const std::string& what) { if (ctx) ctx->error = what; });

@@ -75,7 +75,7 @@ RenderKnobs read_knobs() {
     k.stream_tail_set = e != nullptr;
     k.stream_tail = e ? strtoull(e, nullptr, 10) : 0;
     k.phase_clock = getenv("GBL_PHASE_CLOCK") != nullptr;
-    k.probe = getenv("GBL_PROBE") != nullptr;
+    k.probe = probing();
     return k;
 }
 

@@ -1,7 +1,10 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
 // api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip) share.  No kernel header is needed to read it.
 #pragma once
+#include <chrono>
+#include <cstdlib>
 #include <string>
+#include <utility>
 
 #include "abi_guard.h"
 #include "gbl_internal.h"
@@ -10,25 +13,38 @@
 gbl_status fail(gbl_ctx* ctx, gbl_status st, std::string what);
 
 // Device memory that lives as long as the context (gbl_destroy frees ctx->allocations): GBL_ERR_OOM when the device is out of
-// memory, GBL_ERR_DEVICE for any other failure, the error text naming `what` (api_context.hip)
+// memory, GBL_ERR_DEVICE for any other failure, the error text naming `what`.  device_free gives it back sooner (api_context.hip)
 gbl_status device_alloc(gbl_ctx* ctx, size_t bytes, const char* what, void** out);
+void device_free(gbl_ctx* ctx, void* p);
 
 // Grow a device buffer of the context to at least `bytes`; what it held is not kept (api_context.hip)
 gbl_status grow(gbl_ctx* ctx, gbl_buf& b, uint64_t bytes, const char* what);
 
-// The tail instance edits and vertex edits share: the instance records, instance bounds and TLAS over `instances` (build_tlas
-// with the context's mesh bounds and roots), uploaded into their reserved regions behind a device synchronisation; then
-// stack_entries, gbl_info's TLAS fields, the AUTO pilot's reset, and `instances` becomes the context's own.  `who` starts the
-// error messages.  A refusal (build_tlas's, or a TLAS beyond the reserved nodes) leaves the context untouched.  (api_context.hip)
-gbl_status rebuild_tlas(gbl_ctx* ctx, std::vector<gbl_instance>& instances, const char* who);
+// GBL_PROBE is set: asked at every probe line and never kept, tests and tools set the variable between calls
+inline bool probing() { return getenv("GBL_PROBE") != nullptr; }
+
+// The clock of the probe lines' phases and of build_ms: the milliseconds since the last lap, or since it was made
+struct LapClock {
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    double lap_ms() {
+        const std::chrono::steady_clock::time_point then = std::exchange(last, std::chrono::steady_clock::now());
+        return std::chrono::duration<double, std::milli>(last - then).count();
+    }
+};
 
 // GBL_ERR_UNSUPPORTED with "`who`: a directional or image based light's power ..." in a scene with a light sized by the scene
-// bound, GBL_OK otherwise: what every edit that can move the bound asks first.  (api_context.hip)
+// bound, GBL_OK otherwise: what every edit that can move the bound asks first.  (api_instances.hip)
 gbl_status refuse_scene_bound_edit(gbl_ctx* ctx, const char* who);
-// Instances which[0 .. count) take to_world[0 .. count): the host mirror refreshed, rebuild_tlas over the edited list, and the raw
-// transform table where the context has one.  Makes no refusal of its own: gbl_update_instances keeps an instance that carries an
-// area light out of it, gbl_update_lights moves exactly those, together with their light.  (api_context.hip)
+// Instances which[0 .. count) take to_world[0 .. count), the tail of every scene edit: the host mirror refreshed, build_tlas over
+// the edited list with the context's mesh bounds and roots, records, bounds and TLAS uploaded into their reserved regions behind
+// a device synchronisation, commit_tlas, the raw transform table where the context has one.  `who` starts the error messages; a
+// refusal (build_tlas's, or a TLAS beyond the reserved nodes) leaves the context untouched.  It makes none of its own:
+// gbl_update_instances keeps an instance that carries an area light out of it, gbl_update_lights moves exactly those.
+// retlas_after_geometry_edit moves none -- a mesh's bound or root has changed -- and waits for the uploads.  (api_instances.hip)
 gbl_status move_instances(gbl_ctx* ctx, const uint32_t* which, uint32_t count, const gbl_trs* to_world, const char* who);
+gbl_status retlas_after_geometry_edit(gbl_ctx* ctx, const char* who);
+// A new TLAS stands in the node array: what the kernels and gbl_info read of it, and the AUTO pilot's reset.  (api_instances.hip)
+void commit_tlas(gbl_ctx* ctx, int32_t root, int depth, size_t nodes, int stack_entries);
 
 // The tie order of every mesh a deferred device edit left pending (gbl_update_vertices_device with GBL_VERTICES_DEFER_ORDER):
 // mirror refreshed, mesh_reference_order on the host, the mesh's tri_order slice uploaded, behind a device synchronisation.

@@ -288,6 +288,8 @@ def test_edited_contexts_render_what_a_fresh_one_and_the_oracle_do(torch, dirs, 
             r = tracer(base_scene, bvh)
             before = li_of(r, exact_ties=True)
             r.update_instances(1, on_device(torch, T), device_tlas=device_tlas)
+            if n == 6 and bvh == "device" and not device_tlas:   # (the host's tree, no hot prefix: the fresh context's figures)
+                assert base.tlas_facts(r) == base.tlas_facts(fresh), (base.tlas_facts(r), base.tlas_facts(fresh))
             for s in SCHEDULES:
                 li = li_of(r, schedule=s, exact_ties=True)
                 assert torch.equal(li, want[s]), (n, bvh, device_tlas, s)

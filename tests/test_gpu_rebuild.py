@@ -185,6 +185,8 @@ def test_smallest_shapes(torch, dirs, name, bvh):
         assert stats == {"nodes": 0, "levels": 0, "leaves": 1, "root_area": 0.0, "node_area": 0.0, "tri_area": 0.0, "node_cost": 0.0, "tri_cost": 0.0}
     if name == "few5":
         assert stats["nodes"] == 1
+        if bvh == "device":
+            assert base.tlas_facts(r) == base.tlas_facts(fresh), (base.tlas_facts(r), base.tlas_facts(fresh))
     assert r.info.blas_depth >= shape["depth"]
     if name == "deep_spiral":
         assert 3 * shape["depth"] > 64

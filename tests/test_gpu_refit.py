@@ -105,6 +105,13 @@ def tlas_slice(r, bvh):
     return slice(n - cap, n) if bvh == "host" else slice(0, cap)
 
 
+def tlas_facts(r):
+    """What an edit's TLAS tail publishes besides the tables: gbl_info's tlas_nodes and tlas_depth, and stack_entries.  An edited
+    context is compared with a fresh one under the device builder, where neither holds a hot prefix, and on few5, whose one-node
+    tree a refit cannot leave at another depth than a fresh build's."""
+    return int(r.info.tlas_nodes), int(r.info.tlas_depth), int(r._instances_raw()["stack_entries"])
+
+
 def blas_bytes(nodes, where):
     """The node array's bytes without the TLAS's reserved records."""
     keep = np.ones(len(nodes), bool)
@@ -243,6 +250,8 @@ def test_edited_context_renders_what_a_fresh_one_and_the_oracle_do(torch, dirs, 
     before = {(bvh, s): li_of(edited[bvh], schedule=s, exact_ties=True) for bvh in BUILDERS for s in SCHEDULES}
     for bvh in BUILDERS:
         edit_all(edited[bvh], scene_b, only=[1])   # mesh 0 is the floor
+    if name == "few5":
+        assert tlas_facts(edited["device"]) == tlas_facts(fresh["device"]), (how, tlas_facts(edited["device"]), tlas_facts(fresh["device"]))
     for schedule in SCHEDULES:
         for bvh in BUILDERS:
             li = li_of(edited[bvh], schedule=schedule, exact_ties=True)

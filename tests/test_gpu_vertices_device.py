@@ -168,6 +168,8 @@ def test_a_device_edit_renders_what_a_fresh_context_and_the_oracle_do(torch, dir
         edited, fresh = tracer(scene_a, bvh), tracer(scene_b, bvh)
         before = li_of(edited, exact_ties=True)
         edited.update_vertices(1, PB)   # mesh 0 is the floor
+        if name == "few5" and bvh == "device":
+            assert base.tlas_facts(edited) == base.tlas_facts(fresh), (how, base.tlas_facts(edited), base.tlas_facts(fresh))
         for schedule in SCHEDULES:
             li = li_of(edited, schedule=schedule, exact_ties=True)
             assert torch.equal(li, li_of(fresh, schedule=schedule, exact_ties=True)), (name, how, bvh, schedule)
