@@ -240,6 +240,9 @@ void keep_for_edits(gbl_ctx* ctx, const gbl_scene_desc* desc, const PackedScene&
     ctx->light_instances.assign(desc->num_lights, std::vector<uint32_t>());
     for (uint32_t i = 0; i < desc->num_instances; ++i)
         if (desc->instances[i].area_light >= 0) ctx->light_instances[desc->instances[i].area_light].push_back(i);
+    // images: gbl_update_image* (api_images.hip)
+    ctx->h_images.assign(desc->images, desc->images + desc->num_images);
+    ctx->image_taps.assign(desc->num_images, gbl_ctx::ImageTaps());
 }
 
 // gbl_info but scene_bytes, which the uploads have summed
@@ -356,6 +359,8 @@ void gbl_destroy(gbl_ctx* ctx) {
     for (hipEvent_t ev : ctx->light_ev)
         if (ev) (void)hipEventDestroy(ev);   // (hipHostFree below waits for whatever upload still reads the staging)
     if (ctx->light_stage) (void)hipHostFree(ctx->light_stage);
+    for (const gbl_ctx::ImageTaps& taps : ctx->image_taps)
+        if (taps.uploaded) (void)hipEventDestroy(taps.uploaded);   // (the tables themselves are among ctx->allocations)
     for (int i = 0; i < gbl_ctx::kTimingRing; ++i)
         for (int k = 0; k < 3; ++k)
             if (ctx->t_ev[i][k]) (void)hipEventDestroy(ctx->t_ev[i][k]);

@@ -21,6 +21,7 @@
 #include "kernels/refit_args.h"
 #include "kernels/vertices_args.h"
 #include "kernels/query_args.h"
+#include "kernels/pyramid_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -141,6 +142,17 @@ struct gbl_ctx {
     hipEvent_t light_ev[4] = {};
     unsigned light_edits = 0;
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
+    // what gbl_update_image* needs to build an image's pyramid again (api_images.hip, kernels/pyramid.h)
+    std::vector<gbl_image> h_images;         // gbl_create's records: an edit changes texels only (gbl_get_image)
+    struct ImageTaps {                       // per image, built at its first edit: resizeImage's taps of every level >= 1 ...
+        bool built = false;
+        std::vector<uint32_t> h_words;       // ... on the host: per level s_weight, t_weight (floats), s_index, t_index (int32) ...
+        uint32_t* d_words = nullptr;         // ... and on the device, uploaded once on the first edit's stream
+        hipEvent_t uploaded = nullptr;       // ... recorded behind that upload: an edit on another stream waits for it
+        struct Level { uint32_t s_weight, t_weight, s_index, t_index; int32_t n; };   // offsets into the words
+        std::vector<Level> levels;           // [l - 1] for level l
+    };
+    std::vector<ImageTaps> image_taps;
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
     static const int kTimingRing = 64;
@@ -228,6 +240,8 @@ void gbl_launch_temporal_accumulate_motion(bool spatial, const float4* cl, const
 // one-ray-per-lane measurement form (-DGBL_QUERY_PLAIN), which takes the whole stack in LDS and no hot prefix.
 gbl_query_kernel gbl_kernel_query(bool any, bool ext, bool ties, bool normal);
 bool gbl_query_plain(void);
+// kernels_pyramid.hip: one level of an edited image's MIP pyramid from the level above it (kernels/pyramid.h)
+void gbl_launch_pyramid_level(const PyramidArgs& a, hipStream_t stream);
 // kernels_refit.hip: the passes of gbl_update_vertices (kernels/refit.h)
 void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade* tri_shade, const float* pos, uint32_t num_vertices, uint32_t first,
                            uint32_t count, hipStream_t stream);

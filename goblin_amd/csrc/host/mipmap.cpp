@@ -11,12 +11,12 @@
 #include <vector>
 
 #include "../../../include/goblin_hip.h"
+#include "mipmap_taps.h"
 
 namespace gbl_host_detail {
 
 namespace {
 
-inline int floor_int(float f) { return static_cast<int>(floorf(f)); }
 inline bool is_pow2(uint32_t n) { return (n & (n - 1)) == 0; }
 inline uint32_t round_up_pow2(uint32_t n) {
     n--;
@@ -33,31 +33,15 @@ inline float goblin_log2(float n) {
     static const float inv_log2 = 1.0f / logf(2.0f);
     return logf(n) * inv_log2;
 }
-inline float gaussian(float x, float w, float falloff = 2.0f) { return std::max(0.0f, expf(-falloff * x * x) - expf(-falloff * w * w)); }
 
-// resizeImage<T>, GoblinTexture.cpp:531-597
+// resizeImage<T>, GoblinTexture.cpp:531-597 (its tap step: mipmap_taps.h)
 std::vector<float> resize_image(const std::vector<float>& src, int sw, int sh, int dw, int dh, int channels) {
-    const float filter_width = floorf(std::max(2.0f, std::max(static_cast<float>(sw) / static_cast<float>(dw), static_cast<float>(sh) / static_cast<float>(dh))));
+    const float filter_width = resize_filter_width(sw, sh, dw, dh);
     const int n = floor_int(filter_width) * 2;
     std::vector<float> s_weight(static_cast<size_t>(dw) * n), t_weight(static_cast<size_t>(dh) * n);
     std::vector<int> s_index(dw), t_index(dh);
-    auto taps = [&](int count, int src_size, std::vector<float>& weight, std::vector<int>& index) {
-        for (int s = 0; s < count; ++s) {
-            const float center = (static_cast<float>(s) + 0.5f) / count * src_size;
-            index[s] = floor_int(center - filter_width + 0.5f);
-            float sum = 0.0f;
-            const int off = s * n;
-            for (int i = 0; i < n; ++i) {
-                const float p = index[s] + 0.5f + i;
-                weight[off + i] = gaussian(p - center, filter_width);
-                sum += weight[off + i];
-            }
-            const float inv = 1.0f / sum;
-            for (int i = 0; i < n; ++i) weight[off + i] *= inv;
-        }
-    };
-    taps(dw, sw, s_weight, s_index);
-    taps(dh, sh, t_weight, t_index);
+    resize_taps(dw, sw, filter_width, n, s_weight.data(), s_index.data());
+    resize_taps(dh, sh, filter_width, n, t_weight.data(), t_index.data());
     const int live = channels == 4 ? 3 : channels;   // Color: rgb accumulate, alpha stays Color(0.0f).a = 1
     std::vector<float> dst(static_cast<size_t>(dw) * dh * channels, 0.0f);
     for (int t = 0; t < dh; ++t) {

@@ -358,6 +358,58 @@ class HipPathTracer:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return {"records": records, "cdf": cdf, "pick_pdf": pick, "total": n}
 
+    def _image_record(self, image):
+        d = self.scene.desc
+        if not 0 <= int(image) < d.num_images:
+            raise ValueError("image %r out of range: the scene holds %d" % (image, d.num_images))
+        return d.images[int(image)]
+
+    def update_image(self, image, texels, stream=None):
+        """Give image ``image`` (its index in the scene's images) a new level 0 and build the MIP levels above it on the device
+        (gbl_update_image_device / gbl_update_image).  ``texels``: (height, width, channels) float32 in the layout the context
+        holds -- already converted, sides powers of two, 4 channels for a colour image; (height, width) also for a float image.
+
+        A contiguous float32 torch tensor on the tracer's device is read where it lies; a numpy array goes through the host
+        form; anything else is a ValueError.  Queued on ``stream`` (a torch stream; the current one by default) without a
+        synchronisation.  Width, height and channels cannot change, and an image an image based light reads is refused."""
+        im = self._image_record(image)
+        shapes = [(im.height, im.width, im.channels)] + ([(im.height, im.width)] if im.channels == 1 else [])
+        torch = _torch()
+        if isinstance(texels, torch.Tensor):
+            if texels.dtype != torch.float32 or texels.device != self.device or not texels.is_contiguous():
+                raise ValueError("texels must be a contiguous float32 tensor on %s, got %s on %s%s" %
+                                 (self.device, texels.dtype, texels.device, "" if texels.is_contiguous() else ", not contiguous"))
+            on_device, keep = True, texels
+        elif isinstance(texels, np.ndarray):
+            on_device, keep = False, np.ascontiguousarray(texels, np.float32)
+        else:
+            raise ValueError("texels must be a torch tensor on %s or a numpy array, got %s" % (self.device, type(texels).__name__))
+        if tuple(keep.shape) not in shapes:
+            raise ValueError("texels of image %d must have shape %s, got %s" % (image, " or ".join(map(str, shapes)), tuple(keep.shape)))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if on_device:
+            st = self.lib.gbl_update_image_device(self.handle, int(image), keep.data_ptr(), s.cuda_stream)
+        else:
+            st = self.lib.gbl_update_image(self.handle, int(image), keep.ctypes.data, s.cuda_stream)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+
+    def image(self, image):
+        """The image as the context holds it now (gbl_get_image): its gbl_image record (texel_offset 0) and one
+        (height_l, width_l, channels) float32 array per level, level 0 first.  Synchronises the device."""
+        im = self._image_record(image)
+        sizes = [(max(1, im.height >> l), max(1, im.width >> l), im.channels) for l in range(im.levels)]
+        pool = np.empty(sum(h * w * c for h, w, c in sizes), np.float32)
+        record = _abi.gbl_image()
+        st = self.lib.gbl_get_image(self.handle, int(image), C.byref(record), pool.ctypes.data)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        levels, at = [], 0
+        for h, w, c in sizes:
+            levels.append(pool[at:at + h * w * c].reshape(h, w, c))
+            at += h * w * c
+        return record, levels
+
     def _query_flags(self, kind, exact_ties, normals):
         if kind not in ("closest", "any"):
             raise ValueError("kind must be 'closest' or 'any', got %r" % (kind,))

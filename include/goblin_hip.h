@@ -924,6 +924,38 @@ gbl_status gbl_get_lights(const gbl_ctx* ctx, uint32_t first, uint32_t count, gb
  * Synchronises the device when it copies. */
 gbl_status gbl_selftest_lights(gbl_ctx* ctx, void* records_out, float* cdf_out, float* pick_pdf_out, uint64_t* total);
 
+/* Image edit: image `image` of gbl_scene_desc.images takes a new level 0 and the MIP levels above it are built again on the
+ * device.  level0 holds width * height * channels floats in level 0's layout as the context holds that image -- what the loader
+ * leaves behind: texels already through ImageTexture::convertTexel (channel pick and gamma done), sides already powers of two, a
+ * 4-channel image carrying its alpha, a float texture one channel.  Width, height, levels, channels and the image's place in
+ * the texel pool stay.  After GBL_OK and in stream order the image's texels on the device are what gbl_create uploads for a
+ * description holding this level 0 under a pyramid built as the loader builds it (level 0 the caller's, copied verbatim; level
+ * l >= 1 resizeImage of level l - 1; alpha 1 on every level >= 1), bit for bit for finite level-0 texels whose pyramid stays
+ * finite, and every render, AOV pass and query queued afterwards equals the same call on such a fresh context, bit for bit.
+ * Non-finite texels are not validated (gbl_create does not validate them either): where the host's pyramid has a NaN the
+ * device's has one too, of unspecified bits.
+ *  - Both forms are asynchronous on `stream` (a hipStream_t, NULL for the null stream) and synchronise nothing: work queued on
+ *    that stream before the call keeps the old image, work queued after it sees the new one.  A caller who renders on another
+ *    stream orders the two itself.
+ *  - gbl_update_image_device copies level 0 device to device and launches one kernel per level.  gbl_update_image differs only
+ *    in copying level 0 from the caller's (pageable) host memory, which is read before the call returns.
+ *  - resizeImage's tap weights depend on the level sizes only: the host computes them at the image's first edit, with the expf
+ *    the loader uses, and the context keeps them on the device (that first edit allocates, and uploads them on `stream`).
+ *  - GBL_SCHEDULE_AUTO measures its rays per path again: a mask's alpha may be read from an image.
+ * Refusals, in this order, nothing queued and the context untouched: GBL_ERR_INVALID for a NULL ctx or pointer; GBL_ERR_INVALID
+ * for an image past the context's images (every image of a scene without any); for the device form a pointer that is not device
+ * or managed memory of the context's device, or whose allocation ends before level 0's bytes (GBL_ERR_INVALID; a plain host
+ * pointer is refused before anything reads it); GBL_ERR_UNSUPPORTED, naming the light, for an image that a GBL_LIGHT_IBL light
+ * reads -- also when a texture reads it as well: the light's sampling distribution, average radiance and power are packed from
+ * these texels when the context is created.  An image that nothing reads is accepted. */
+gbl_status gbl_update_image_device(gbl_ctx* ctx, uint32_t image, const float* d_level0 /* device */, void* stream);
+gbl_status gbl_update_image(gbl_ctx* ctx, uint32_t image, const float* level0 /* host */, void* stream);
+/* The image as the context holds it now: its record into *info_out and / or its whole pyramid -- level 0 first, each level
+ * row-major, the sum over the levels of max(1, w >> l) * max(1, h >> l) * channels floats -- into texels_out (host memory).
+ * info_out->texel_offset is 0: it counts from the start of texels_out.  Either pointer may be NULL; copying texels
+ * synchronises the device.  GBL_ERR_INVALID, nothing touched, for a NULL ctx, an image out of range, and two NULL pointers. */
+gbl_status gbl_get_image(gbl_ctx* ctx, uint32_t image, gbl_image* info_out /* or NULL */, float* texels_out /* host, or NULL */);
+
 /* Scene queries: Scene::intersect (GBL_QUERY_CLOSEST) or Scene::occluded (GBL_QUERY_ANY) for n caller rays in DEVICE memory,
  * against the context as it is now -- every gbl_update_instances*, gbl_update_vertices*, gbl_rebuild_mesh edit taken so far is
  * seen.  What a simulation step on the GPU asks between two edits: collision probes, ground snapping, line of sight, picking,
