@@ -243,6 +243,7 @@ void keep_for_edits(gbl_ctx* ctx, const gbl_scene_desc* desc, const PackedScene&
     // images: gbl_update_image* (api_images.hip)
     ctx->h_images.assign(desc->images, desc->images + desc->num_images);
     ctx->image_taps.assign(desc->num_images, gbl_ctx::ImageTaps());
+    ctx->environment.assign(desc->num_lights, gbl_ctx::Environment());
 }
 
 // gbl_info but scene_bytes, which the uploads have summed
@@ -361,6 +362,11 @@ void gbl_destroy(gbl_ctx* ctx) {
     if (ctx->light_stage) (void)hipHostFree(ctx->light_stage);
     for (const gbl_ctx::ImageTaps& taps : ctx->image_taps)
         if (taps.uploaded) (void)hipEventDestroy(taps.uploaded);   // (the tables themselves are among ctx->allocations)
+    for (const gbl_ctx::Environment& env : ctx->environment)
+        for (hipEvent_t ev : {env.uploaded, env.power_read})
+            if (ev) (void)hipEventDestroy(ev);
+    if (ctx->env_power_uploaded) (void)hipEventDestroy(ctx->env_power_uploaded);
+    if (ctx->env_pinned) (void)hipHostFree(ctx->env_pinned);   // (it waits for whatever copy still uses it)
     for (int i = 0; i < gbl_ctx::kTimingRing; ++i)
         for (int k = 0; k < 3; ++k)
             if (ctx->t_ev[i][k]) (void)hipEventDestroy(ctx->t_ev[i][k]);

@@ -4,7 +4,8 @@
 // image's texels equal what gbl_create uploads for a description whose pyramid csrc/host/mipmap.cpp built from that level 0, bit
 // for bit.  resizeImage's tap tables depend on the level sizes only: the host makes them at the image's first edit with the
 // function the loader makes them with (csrc/host/mipmap_taps.h) and the context keeps them on the device.  Nothing is
-// synchronised.  gbl_get_image reads a record and a pyramid back.
+// synchronised.  gbl_get_image reads a record and a pyramid back.  The copy and the launches are one function,
+// queue_image_pyramid, which the environment edits (api_environment.hip) queue as well.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -76,6 +77,44 @@ gbl_status ensure_taps(gbl_ctx* ctx, uint32_t image, const char* who, hipStream_
     return GBL_OK;
 }
 
+}   // namespace
+
+// (gbl_host.h) What both image edits and both environment edits queue: the tap tables at the image's first edit, level 0's copy,
+// then one launch per level above it
+gbl_status queue_image_pyramid(gbl_ctx* ctx, uint32_t image, const float* level0, bool on_device, hipStream_t stream, const char* who) {
+    const gbl_image& gi = ctx->h_images[image];
+    gbl_status st = GBL_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((st = ensure_taps(ctx, image, who, stream)) != GBL_OK) return st;
+    const gbl_ctx::ImageTaps& taps = ctx->image_taps[image];
+    float* const texels = const_cast<float*>(ctx->scene.texels) + gi.texel_offset;
+    // (a pageable source is read before the copy call returns, as gbl_render_motion's table is)
+    HIP_TRY(ctx, hipMemcpyAsync(texels, level0, level_floats(gi, 0) * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    if (taps.uploaded) HIP_TRY(ctx, hipStreamWaitEvent(stream, taps.uploaded, 0));
+    uint64_t src = 0;
+    for (uint32_t l = 1; l < gi.levels; ++l) {   // level l reads what the launch before it wrote
+        const gbl_ctx::ImageTaps::Level& at = taps.levels[l - 1];
+        const uint64_t dst = src + level_floats(gi, l - 1);
+        PyramidArgs a;
+        a.src = texels + src;
+        a.dst = texels + dst;
+        a.s_weight = reinterpret_cast<const float*>(taps.d_words + at.s_weight);
+        a.t_weight = reinterpret_cast<const float*>(taps.d_words + at.t_weight);
+        a.s_index = reinterpret_cast<const int32_t*>(taps.d_words + at.s_index);
+        a.t_index = reinterpret_cast<const int32_t*>(taps.d_words + at.t_index);
+        a.sw = static_cast<int32_t>(level_side(gi.width, l - 1)), a.sh = static_cast<int32_t>(level_side(gi.height, l - 1));
+        a.dw = static_cast<int32_t>(level_side(gi.width, l)), a.dh = static_cast<int32_t>(level_side(gi.height, l));
+        a.n = at.n;
+        a.channels = static_cast<int32_t>(gi.channels);
+        gbl_launch_pyramid_level(a, stream);
+        src = dst;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return GBL_OK;
+}
+
+namespace {
+
 // The image based light that reads the image, or -1
 int ibl_reader(const gbl_ctx* ctx, uint32_t image) {
     for (size_t i = 0; i < ctx->h_lights.size(); ++i)
@@ -101,33 +140,7 @@ gbl_status gbl_update_image_impl(gbl_ctx* ctx, uint32_t image, const float* leve
         return fail(ctx, GBL_ERR_UNSUPPORTED, std::string(who) + ": image " + std::to_string(image) + " is read by image based light " + std::to_string(light) +
                                               ", whose sampling distribution, average radiance and power are packed from its texels when the context is created; "
                                               "re-create the context instead");
-    const hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((st = ensure_taps(ctx, image, who, stream)) != GBL_OK) return st;
-    const gbl_ctx::ImageTaps& taps = ctx->image_taps[image];
-    float* const texels = const_cast<float*>(ctx->scene.texels) + gi.texel_offset;
-    // (a pageable source is read before the copy call returns, as gbl_render_motion's table is)
-    HIP_TRY(ctx, hipMemcpyAsync(texels, level0, bytes0, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-    if (taps.uploaded) HIP_TRY(ctx, hipStreamWaitEvent(stream, taps.uploaded, 0));
-    uint64_t src = 0;
-    for (uint32_t l = 1; l < gi.levels; ++l) {   // level l reads what the launch before it wrote
-        const gbl_ctx::ImageTaps::Level& at = taps.levels[l - 1];
-        const uint64_t dst = src + level_floats(gi, l - 1);
-        PyramidArgs a;
-        a.src = texels + src;
-        a.dst = texels + dst;
-        a.s_weight = reinterpret_cast<const float*>(taps.d_words + at.s_weight);
-        a.t_weight = reinterpret_cast<const float*>(taps.d_words + at.t_weight);
-        a.s_index = reinterpret_cast<const int32_t*>(taps.d_words + at.s_index);
-        a.t_index = reinterpret_cast<const int32_t*>(taps.d_words + at.t_index);
-        a.sw = static_cast<int32_t>(level_side(gi.width, l - 1)), a.sh = static_cast<int32_t>(level_side(gi.height, l - 1));
-        a.dw = static_cast<int32_t>(level_side(gi.width, l)), a.dh = static_cast<int32_t>(level_side(gi.height, l));
-        a.n = at.n;
-        a.channels = static_cast<int32_t>(gi.channels);
-        gbl_launch_pyramid_level(a, stream);
-        src = dst;
-    }
-    HIP_TRY(ctx, hipGetLastError());
+    if ((st = queue_image_pyramid(ctx, image, level0, on_device, static_cast<hipStream_t>(stream_), who)) != GBL_OK) return st;
     ctx->auto_rays_per_path.clear();   // a mask's alpha may be read from an image: AUTO measures its rays per path again
     return GBL_OK;
 }

@@ -63,20 +63,23 @@ gbl_status check_values(gbl_ctx* ctx, uint32_t i, const gbl_light& want) {
     return GBL_OK;
 }
 
-// Where the three tables sit in one staging slot
+// Where the three tables, and the powers behind them, sit in one staging slot
 struct StageLayout {
-    size_t lights, cdf, pick, slot;
+    size_t lights, cdf, pick, power, slot;
     explicit StageLayout(size_t n) {
         const auto pad = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
         lights = 0;
         cdf = pad(n * sizeof(DevLight));
         pick = cdf + pad((n + 1) * sizeof(float));
-        slot = pick + pad(std::max<size_t>(1, n) * sizeof(float));
+        power = pick + pad(std::max<size_t>(1, n) * sizeof(float));
+        slot = power + pad(std::max<size_t>(1, n) * sizeof(float));
     }
 };
 
 // The uploads, in the stream's order: a slot of the pinned staging is written again only after the upload that last read it
-gbl_status queue_tables(gbl_ctx* ctx, const std::vector<DevLight>& lights, const std::vector<float>& cdf, const std::vector<float>& pick, hipStream_t stream) {
+// The powers go to the device only where an environment edit has made a table of them (gbl_ctx::d_light_power), which the next one reads
+gbl_status queue_tables(gbl_ctx* ctx, const std::vector<DevLight>& lights, const std::vector<float>& cdf, const std::vector<float>& pick, const std::vector<float>& power,
+                        hipStream_t stream) {
     const StageLayout at(lights.size());
     if (!ctx->light_stage) {
         void* p = nullptr;
@@ -90,10 +93,15 @@ gbl_status queue_tables(gbl_ctx* ctx, const std::vector<DevLight>& lights, const
     memcpy(s + at.lights, lights.data(), lights.size() * sizeof(DevLight));
     memcpy(s + at.cdf, cdf.data(), cdf.size() * sizeof(float));
     memcpy(s + at.pick, pick.data(), pick.size() * sizeof(float));
+    memcpy(s + at.power, power.data(), power.size() * sizeof(float));
     const DevScene& sc = ctx->scene;
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<DevLight*>(sc.lights), s + at.lights, lights.size() * sizeof(DevLight), hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(sc.light_cdf), s + at.cdf, cdf.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(sc.light_pick_pdf), s + at.pick, pick.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (ctx->d_light_power) {
+        if (ctx->env_power_uploaded) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->env_power_uploaded, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_light_power, s + at.power, power.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->light_ev[slot], stream));
     ++ctx->light_edits;
     return GBL_OK;
@@ -130,13 +138,15 @@ gbl_status gbl_update_lights_impl(gbl_ctx* ctx, uint32_t first, uint32_t count, 
             to_world.push_back(lights[i].to_world);
         }
     }
+    // an environment edit left its light's power on the device: h_light_power waits for it here (gbl_host.h)
+    if ((st = settle_environment_power(ctx)) != GBL_OK) return st;
     std::vector<DevLight> records = ctx->h_dev_lights;
     std::vector<float> power = ctx->h_light_power, cdf, pick;
     repack_lights(lights, first, count, ctx->bound_lo, ctx->bound_hi, &records, &power, &cdf, &pick);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // (build_tlas's refusal of a transform the reference cannot invert comes from here, before anything is written)
     if (!which.empty() && (st = move_instances(ctx, which.data(), static_cast<uint32_t>(which.size()), to_world.data(), kWho)) != GBL_OK) return st;
-    if ((st = queue_tables(ctx, records, cdf, pick, static_cast<hipStream_t>(stream))) != GBL_OK) return st;
+    if ((st = queue_tables(ctx, records, cdf, pick, power, static_cast<hipStream_t>(stream))) != GBL_OK) return st;
     std::copy(lights, lights + count, ctx->h_lights.begin() + first);
     ctx->h_dev_lights.swap(records);
     ctx->h_light_power.swap(power);

@@ -1,5 +1,5 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
-// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip) share.  No kernel header is needed to read it.
+// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip, api_images.hip, api_environment.hip) share.  No kernel header is needed to read it.
 #pragma once
 #include <chrono>
 #include <cstdlib>
@@ -68,6 +68,16 @@ gbl_status write_instance_table(gbl_ctx* ctx, uint32_t first, uint32_t count);
 // GBL_OK when `p` is device or managed memory of the context's device whose allocation holds `bytes` from p on; GBL_ERR_INVALID
 // with "`who`: `what` ..." otherwise, the sticky error a plain host pointer leaves cleared.  Touches no device memory.  (api_geometry.hip)
 gbl_status check_device_pointer(gbl_ctx* ctx, const void* p, uint64_t bytes, const std::string& who, const char* what);
+
+// Image `image` takes level 0 from `level0` (device memory, or the caller's pageable host memory) and the levels above it are
+// launched, all on `stream`: the image's tap tables made and uploaded at its first edit, the copy, one pyramid launch per level.
+// The caller has validated everything; `who` names it in an allocation failure.  (api_images.hip)
+gbl_status queue_image_pyramid(gbl_ctx* ctx, uint32_t image, const float* level0, bool on_device, hipStream_t stream, const char* who);
+
+// h_light_power, h_light_cdf and h_light_pick_pdf brought up to the device's after environment edits, whose powers are worked out
+// on the device: waits for each pending 4-byte read-back's event, then packs the distribution again on the host.  Nothing to do
+// (and nothing waited for) when no light's power is pending.  gbl_update_lights calls it before it packs.  (api_environment.hip)
+gbl_status settle_environment_power(gbl_ctx* ctx);
 
 // A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it first
 template <class K>

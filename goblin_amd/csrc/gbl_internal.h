@@ -22,6 +22,7 @@
 #include "kernels/vertices_args.h"
 #include "kernels/query_args.h"
 #include "kernels/pyramid_args.h"
+#include "kernels/environment_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -153,6 +154,20 @@ struct gbl_ctx {
         std::vector<Level> levels;           // [l - 1] for level l
     };
     std::vector<ImageTaps> image_taps;
+    // what gbl_update_environment* needs to make an image based light's tables again (api_environment.hip, kernels/environment.h)
+    struct Environment {                     // per light, built at an image based light's first edit: sin(theta) per row of its
+        bool built = false;                  // distribution (scene_prep.h ibl_sin_theta) ...
+        std::vector<float> h_sin_theta;      // ... on the host, the upload's source ...
+        float* d_sin_theta = nullptr;        // ... and on the device, uploaded once on the first edit's stream
+        hipEvent_t uploaded = nullptr;       // ... recorded behind that upload: an edit on another stream waits for it
+        hipEvent_t power_read = nullptr;     // recorded behind the last edit's copy of the light's new power into env_pinned
+        bool power_pending = false;          // h_light_power's entry is older than the device's (settle_environment_power)
+    };
+    std::vector<Environment> environment;
+    float* d_light_power = nullptr;          // the lights' powers on the device, made from h_light_power at the first environment edit and
+                                             // kept by every environment edit (its kernel) and light edit (an upload) after that
+    float* env_pinned = nullptr;             // pinned, 2 floats per light: that first upload's source, then the powers read back
+    hipEvent_t env_power_uploaded = nullptr; // recorded behind d_light_power's first upload
     uint32_t* wf_host_flags = nullptr;   // pinned
     // ring of event triples for gbl_get_timings
     static const int kTimingRing = 64;
@@ -242,6 +257,9 @@ gbl_query_kernel gbl_kernel_query(bool any, bool ext, bool ties, bool normal);
 bool gbl_query_plain(void);
 // kernels_pyramid.hip: one level of an edited image's MIP pyramid from the level above it (kernels/pyramid.h)
 void gbl_launch_pyramid_level(const PyramidArgs& a, hipStream_t stream);
+// kernels_environment.hip: an image based light's distribution, power and the pick distribution from its image's pyramid
+// (kernels/environment.h).  parts: 2 func and the rows' CDFs, 4 the tail (api_environment.hip parts_asked)
+void gbl_launch_environment(const EnvironmentArgs& a, unsigned parts, hipStream_t stream);
 // kernels_refit.hip: the passes of gbl_update_vertices (kernels/refit.h)
 void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade* tri_shade, const float* pos, uint32_t num_vertices, uint32_t first,
                            uint32_t count, hipStream_t stream);

@@ -1265,9 +1265,10 @@ void pack_ibl_distribution(const IblTexels& tx, PackedScene* out, DevLight* dl) 
     const int dw = tx.width(level), dh = tx.height(level);
     dl->dist_offset = static_cast<uint32_t>(out->ibl_dist.size());
     dl->dist_w = static_cast<uint32_t>(dw), dl->dist_h = static_cast<uint32_t>(dh);
-    std::vector<float> rows_block, row_integrals, marginal_block;
+    std::vector<float> rows_block, row_integrals, marginal_block, sin_table;
+    ibl_sin_theta(static_cast<uint32_t>(dh), &sin_table);
     for (int r = 0; r < dh; ++r) {
-        const float sin_theta = sinf((static_cast<float>(r) + 0.5f) / static_cast<float>(dh) * kPi);
+        const float sin_theta = sin_table[r];
         std::vector<float> f(dw);
         for (int c = 0; c < dw; ++c) {
             const float rgb[3] = {tx.at(level, c, r, 0), tx.at(level, c, r, 1), tx.at(level, c, r, 2)};
@@ -1309,8 +1310,7 @@ float attach_ibl_texels(const gbl_scene_desc& d, const gbl_light& gl, const Aabb
                  (1.0f - ds) * (dt)*tx.at(max_level, s0, t0 + 1, c) + (ds) * (dt)*tx.at(max_level, s0 + 1, t0 + 1, c);
     pack_ibl_distribution(tx, out, dl);
     // ImageBasedLight::power (:606-613): mAverageRadiance * PI * (4 PI r^2) over the scene's bounding sphere
-    const float radius = bounding_radius(scene_bound);
-    return power_of(avg, kPi, 4.0f * kPi * radius * radius);
+    return power_of(avg, kPi, ibl_sphere_area(scene_bound.lo, scene_bound.hi));
 }
 
 // Per light: the part the scene's geometry decides (emitting triangles, texels, the Whitted quota), then pack_light for the part
@@ -1449,6 +1449,20 @@ void hot_prefix(const gbl_scene_desc& d, PackedScene* out) {
 }
 
 }  // namespace
+
+// One statement of what an image based light's tables take from the host besides its texels: pack_scene's and
+// gbl_update_environment's (api_environment.hip)
+void ibl_sin_theta(uint32_t dist_h, std::vector<float>* table) {
+    table->resize(dist_h);
+    for (uint32_t r = 0; r < dist_h; ++r) (*table)[r] = sinf((static_cast<float>(r) + 0.5f) / static_cast<float>(dist_h) * kPi);
+}
+
+float ibl_sphere_area(const float bound_lo[3], const float bound_hi[3]) {
+    Aabb scene_bound;
+    for (int k = 0; k < 3; ++k) scene_bound.lo[k] = bound_lo[k], scene_bound.hi[k] = bound_hi[k];
+    const float radius = bounding_radius(scene_bound);
+    return 4.0f * kPi * radius * radius;
+}
 
 // One statement of each light's packing: pack_scene's and gbl_update_lights'
 float pack_light(const gbl_light& gl, const float bound_lo[3], const float bound_hi[3], float kept_power, DevLight* dl) {

@@ -102,6 +102,12 @@ void pack_light_distribution(const std::vector<float>& power, std::vector<float>
 void repack_lights(const gbl_light* edited, uint32_t first, uint32_t count, const float bound_lo[3], const float bound_hi[3], std::vector<DevLight>* lights,
                    std::vector<float>* power, std::vector<float>* cdf, std::vector<float>* pick_pdf);
 
+// What an image based light's tables take from the host besides its texels, stated once for pack_scene and for
+// gbl_update_environment: sin(theta) at the centre of each of the distribution's dist_h rows (ImageBasedLight's constructor,
+// with the loader's sinf), and the area 4 pi r^2 of the scene bound's sphere that its power is taken over.
+void ibl_sin_theta(uint32_t dist_h, std::vector<float>* table);
+float ibl_sphere_area(const float bound_lo[3], const float bound_hi[3]);
+
 // One mesh's DevTriOrder records (the reference's visiting order, per mesh-local triangle number) and its object bound (the
 // bound of ALL its vertices), as pack_scene makes them: gbl_update_vertices makes them again over edited positions.
 // `positions` is the mesh's first vertex, `indices` its first (mesh-local) index.

@@ -371,7 +371,8 @@ class HipPathTracer:
 
         A contiguous float32 torch tensor on the tracer's device is read where it lies; a numpy array goes through the host
         form; anything else is a ValueError.  Queued on ``stream`` (a torch stream; the current one by default) without a
-        synchronisation.  Width, height and channels cannot change, and an image an image based light reads is refused."""
+        synchronisation.  Width, height and channels cannot change, and an image an image based light reads is refused:
+        ``update_environment`` is the edit for it."""
         im = self._image_record(image)
         shapes = [(im.height, im.width, im.channels)] + ([(im.height, im.width)] if im.channels == 1 else [])
         torch = _torch()
@@ -393,6 +394,59 @@ class HipPathTracer:
             st = self.lib.gbl_update_image(self.handle, int(image), keep.ctypes.data, s.cuda_stream)
         if st != _abi.GBL_OK:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+
+    def _environment_light(self, light):
+        d = self.scene.desc
+        if not 0 <= int(light) < d.num_lights:
+            raise ValueError("light %r out of range: the scene holds %d" % (light, d.num_lights))
+        if d.lights[int(light)].type != _abi.GBL_LIGHT_IBL:
+            raise ValueError("light %d is not an image based light (type %d)" % (light, d.lights[int(light)].type))
+        return d.lights[int(light)]
+
+    def update_environment(self, light, texels, stream=None):
+        """Give the image of image based light ``light`` (its index in the scene's lights) a new level 0 and make again, on the
+        device, all that the context derives from it: the image's MIP pyramid, the light's sampling distribution, its power and
+        the pick distribution over the lights (gbl_update_environment_device / gbl_update_environment).  ``texels``: (height,
+        width, 4) float32 in the layout the context holds -- sides powers of two, the light's filter colour multiplied in.
+
+        A contiguous float32 torch tensor on the tracer's device is read where it lies; a numpy array goes through the host
+        form; anything else is a ValueError.  Queued on ``stream`` (a torch stream; the current one by default) without a
+        synchronisation; the next ``update_lights`` waits until the edit has run, for the light's new power."""
+        im = self._image_record(self._environment_light(light).image)
+        shape = (im.height, im.width, 4)
+        torch = _torch()
+        if isinstance(texels, torch.Tensor):
+            if texels.dtype != torch.float32 or texels.device != self.device or not texels.is_contiguous():
+                raise ValueError("texels must be a contiguous float32 tensor on %s, got %s on %s%s" %
+                                 (self.device, texels.dtype, texels.device, "" if texels.is_contiguous() else ", not contiguous"))
+            on_device, keep = True, texels
+        elif isinstance(texels, np.ndarray):
+            if texels.dtype != np.float32:
+                raise ValueError("texels must be float32, got %s" % texels.dtype)
+            on_device, keep = False, np.ascontiguousarray(texels)
+        else:
+            raise ValueError("texels must be a torch tensor on %s or a numpy array, got %s" % (self.device, type(texels).__name__))
+        if tuple(keep.shape) != shape:
+            raise ValueError("texels of light %d must have shape %s, got %s" % (light, shape, tuple(keep.shape)))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if on_device:
+            st = self.lib.gbl_update_environment_device(self.handle, int(light), keep.data_ptr(), s.cuda_stream)
+        else:
+            st = self.lib.gbl_update_environment(self.handle, int(light), keep.ctypes.data, s.cuda_stream)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+
+    def _environment_raw(self, light):
+        """The light's block of the device's distribution table read back (gbl_selftest_environment): a dict of dist (flat
+        float32: the marginal block, then the rows'), level, dist_w and dist_h.  For tests."""
+        floats, dims = C.c_uint64(), (C.c_uint32 * 3)()
+        st = self.lib.gbl_selftest_environment(self.handle, int(light), None, C.byref(floats), C.byref(dims))
+        if st == _abi.GBL_OK:
+            dist = np.zeros(floats.value, np.float32)
+            st = self.lib.gbl_selftest_environment(self.handle, int(light), dist.ctypes.data, None, None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return {"dist": dist, "level": int(dims[0]), "dist_w": int(dims[1]), "dist_h": int(dims[2])}
 
     def image(self, image):
         """The image as the context holds it now (gbl_get_image): its gbl_image record (texel_offset 0) and one

@@ -947,7 +947,8 @@ gbl_status gbl_selftest_lights(gbl_ctx* ctx, void* records_out, float* cdf_out, 
  * or managed memory of the context's device, or whose allocation ends before level 0's bytes (GBL_ERR_INVALID; a plain host
  * pointer is refused before anything reads it); GBL_ERR_UNSUPPORTED, naming the light, for an image that a GBL_LIGHT_IBL light
  * reads -- also when a texture reads it as well: the light's sampling distribution, average radiance and power are packed from
- * these texels when the context is created.  An image that nothing reads is accepted. */
+ * these texels when the context is created; gbl_update_environment* below is the edit for such an image.  An image that nothing
+ * reads is accepted. */
 gbl_status gbl_update_image_device(gbl_ctx* ctx, uint32_t image, const float* d_level0 /* device */, void* stream);
 gbl_status gbl_update_image(gbl_ctx* ctx, uint32_t image, const float* level0 /* host */, void* stream);
 /* The image as the context holds it now: its record into *info_out and / or its whole pyramid -- level 0 first, each level
@@ -955,6 +956,44 @@ gbl_status gbl_update_image(gbl_ctx* ctx, uint32_t image, const float* level0 /*
  * info_out->texel_offset is 0: it counts from the start of texels_out.  Either pointer may be NULL; copying texels
  * synchronises the device.  GBL_ERR_INVALID, nothing touched, for a NULL ctx, an image out of range, and two NULL pointers. */
 gbl_status gbl_get_image(gbl_ctx* ctx, uint32_t image, gbl_image* info_out /* or NULL */, float* texels_out /* host, or NULL */);
+
+/* Environment edit: the image of image based light `light` takes a new level 0, and everything gbl_create derives from those
+ * texels is made again on the device.  The edit is addressed by light: it changes the light's tables, not only texels.  level0
+ * holds width * height * 4 floats in the layout in which the context holds the light's image -- what the loader leaves behind:
+ * sides already powers of two, the light's `filter` colour already multiplied in.  Nothing validates the texels, as in
+ * gbl_create.  After GBL_OK and in stream order these tables equal what a fresh gbl_create holds for a description that differs
+ * only in this level 0 under a pyramid built as the loader builds it -- bit for bit wherever the host's value is not a NaN, and a
+ * NaN of unspecified bits where it is one (a row or an image that sums to zero makes the host's own CDF 0 / 0):
+ *   1. the image's whole pyramid in the texel pool, as gbl_update_image* builds it;
+ *   2. the light's sampling distribution (luminance * sin(theta) of pyramid level max(0, levels - 9), neither side above 256): the
+ *      marginal block over the rows' integrals, then one block per row, each func[n], cdf[n + 1], integral;
+ *   3. the light's power (the 1 x 1 level's radiance over the sphere of the scene bound the context was created with), and with it
+ *      the light pick CDF and the pick probabilities of every light.
+ * The light's record does not change: where its distribution lies and its size depend on the image's size only.  A texture that
+ * reads the same image sees the new texels.
+ *  - Both forms queue everything on `stream` (a hipStream_t, NULL for the null stream) and synchronise nothing: work queued on
+ *    that stream before the call keeps the old environment, work queued after it sees the new one.  gbl_update_environment differs
+ *    only in copying level 0 from the caller's (pageable) host memory, which is read before the call returns.
+ *  - The light's first edit makes sin(theta) per row of its distribution on the host, with the sinf gbl_create uses, and uploads
+ *    it on `stream`; the image's first edit does the same for the pyramid's tap weights; the context's first edit puts the lights'
+ *    powers on the device.  These first edits allocate.
+ *  - The host does not know the light's new power: it is worked out on the device and copied into pinned memory behind an event.
+ *    gbl_update_lights, which packs the pick distribution on the host, waits for that event before it packs -- the one host wait
+ *    this entry adds, paid by the next gbl_update_lights and not by the edit, and over once the edit's kernels have run.
+ *    gbl_update_lights after an environment edit, and the two in the other order, leave the tables of a fresh context given both.
+ *  - GBL_SCHEDULE_AUTO measures its rays per path again.
+ * Refusals, in this order, nothing queued and the context untouched: GBL_ERR_INVALID for a NULL ctx or pointer; GBL_ERR_INVALID
+ * for a light past the context's lights; GBL_ERR_INVALID, naming its type, for a light that is not a GBL_LIGHT_IBL; for the
+ * device form a pointer that is not device or managed memory of the context's device, or whose allocation ends before level 0's
+ * bytes (GBL_ERR_INVALID; a plain host pointer is refused before anything reads it); GBL_ERR_UNSUPPORTED, naming it, when another
+ * image based light reads the same image.  Two image based lights over two images are edited one after the other. */
+gbl_status gbl_update_environment_device(gbl_ctx* ctx, uint32_t light, const float* d_level0 /* device */, void* stream);
+gbl_status gbl_update_environment(gbl_ctx* ctx, uint32_t light, const float* level0 /* host */, void* stream);
+/* Self-test hook: the light's block of the distribution table to host memory -- (2 h + 2) + h (2 w + 2) floats for a distribution
+ * of w x h, the count also in *dist_floats -- and {pyramid level, w, h} in dims_out.  Any out pointer may be NULL; copying
+ * synchronises the device.  GBL_ERR_INVALID for a NULL ctx, a light out of range and a light that is not image based. */
+gbl_status gbl_selftest_environment(gbl_ctx* ctx, uint32_t light, float* dist_out /* host, or NULL */, uint64_t* dist_floats,
+                                    uint32_t dims_out[3] /* level, dist_w, dist_h; or NULL */);
 
 /* Scene queries: Scene::intersect (GBL_QUERY_CLOSEST) or Scene::occluded (GBL_QUERY_ANY) for n caller rays in DEVICE memory,
  * against the context as it is now -- every gbl_update_instances*, gbl_update_vertices*, gbl_rebuild_mesh edit taken so far is
