@@ -240,6 +240,10 @@ void keep_for_edits(gbl_ctx* ctx, const gbl_scene_desc* desc, const PackedScene&
     ctx->light_instances.assign(desc->num_lights, std::vector<uint32_t>());
     for (uint32_t i = 0; i < desc->num_instances; ++i)
         if (desc->instances[i].area_light >= 0) ctx->light_instances[desc->instances[i].area_light].push_back(i);
+    // materials and textures: gbl_update_materials*, gbl_update_textures* (api_materials.hip; h_materials is kept above)
+    ctx->h_textures.assign(desc->textures, desc->textures + desc->num_textures);
+    ctx->mat_records = packed.materials;
+    ctx->tex_records = packed.textures;
     // images: gbl_update_image* (api_images.hip)
     ctx->h_images.assign(desc->images, desc->images + desc->num_images);
     ctx->image_taps.assign(desc->num_images, gbl_ctx::ImageTaps());
@@ -360,6 +364,12 @@ void gbl_destroy(gbl_ctx* ctx) {
     for (hipEvent_t ev : ctx->light_ev)
         if (ev) (void)hipEventDestroy(ev);   // (hipHostFree below waits for whatever upload still reads the staging)
     if (ctx->light_stage) (void)hipHostFree(ctx->light_stage);
+    for (gbl_ctx::EditTable* e : {&ctx->mat_edit, &ctx->tex_edit}) {   // (the row tables themselves are among ctx->allocations)
+        for (hipEvent_t ev : e->ev)
+            if (ev) (void)hipEventDestroy(ev);
+        if (e->rows_uploaded) (void)hipEventDestroy(e->rows_uploaded);
+        if (e->stage) (void)hipHostFree(e->stage);
+    }
     for (const gbl_ctx::ImageTaps& taps : ctx->image_taps)
         if (taps.uploaded) (void)hipEventDestroy(taps.uploaded);   // (the tables themselves are among ctx->allocations)
     for (const gbl_ctx::Environment& env : ctx->environment)

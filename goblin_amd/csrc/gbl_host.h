@@ -1,5 +1,5 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
-// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip, api_images.hip, api_environment.hip) share.  No kernel header is needed to read it.
+// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip, api_images.hip, api_environment.hip, api_materials.hip) share.  No kernel header is needed to read it.
 #pragma once
 #include <chrono>
 #include <cstdlib>

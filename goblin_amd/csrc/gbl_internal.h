@@ -23,6 +23,7 @@
 #include "kernels/query_args.h"
 #include "kernels/pyramid_args.h"
 #include "kernels/environment_args.h"
+#include "kernels/materials_args.h"
 
 // A device buffer of the context, grown on demand (gbl_host.h grow()) and freed by gbl_destroy
 struct gbl_buf {
@@ -142,6 +143,22 @@ struct gbl_ctx {
     unsigned char* light_stage = nullptr;
     hipEvent_t light_ev[4] = {};
     unsigned light_edits = 0;
+    // what gbl_update_materials* and gbl_update_textures* keep beside h_materials (api_materials.hip, scene_prep.h repack_materials /
+    // repack_textures, kernels/materials.h)
+    std::vector<gbl_texture> h_textures;     // the description last set: gbl_create's at first (gbl_get_textures)
+    std::vector<DevMaterial> mat_records;    // what repack_materials / repack_textures pack into: only the records an edit has just
+    std::vector<DevTexture> tex_records;     // packed are read, the others may be older than the device's (a device edit writes none)
+    struct EditTable {                       // per table (0 materials, 1 textures):
+        unsigned char* stage = nullptr;      // pinned staging, kLightSlots copies of the table's records and raw rows ...
+        hipEvent_t ev[4] = {};               // ... each with the event of the upload that last read it
+        unsigned edits = 0;
+        float* d_rows = nullptr;             // the raw rows (materials_args.h) per record on the device: made from the host copy at the
+                                             // first device edit, written by every edit after that
+        std::vector<float> h_rows;           // ... that first upload's source
+        hipEvent_t rows_uploaded = nullptr;  // ... recorded behind it: an edit on another stream waits for it
+        uint32_t stale_first = 0, stale_end = 0;   // the host description of [first .. end) is older than d_rows (refresh_table_mirror)
+    };
+    EditTable mat_edit, tex_edit;
     bool has_images = false;     // the scene holds MIP pyramids (image textures / image based lights)
     // what gbl_update_image* needs to build an image's pyramid again (api_images.hip, kernels/pyramid.h)
     std::vector<gbl_image> h_images;         // gbl_create's records: an edit changes texels only (gbl_get_image)
@@ -260,6 +277,9 @@ void gbl_launch_pyramid_level(const PyramidArgs& a, hipStream_t stream);
 // kernels_environment.hip: an image based light's distribution, power and the pick distribution from its image's pyramid
 // (kernels/environment.h).  parts: 2 func and the rows' CDFs, 4 the tail (api_environment.hip parts_asked)
 void gbl_launch_environment(const EnvironmentArgs& a, unsigned parts, hipStream_t stream);
+// kernels_materials.hip: gbl_update_materials_device / gbl_update_textures_device (kernels/materials.h), one lane per edited record
+void gbl_launch_mat_compose(const MatComposeArgs& a, hipStream_t stream);
+void gbl_launch_tex_compose(const TexComposeArgs& a, hipStream_t stream);
 // kernels_refit.hip: the passes of gbl_update_vertices (kernels/refit.h)
 void gbl_launch_refit_tris(DevTri* tris, DevTriBound* bounds, const DevTriShade* tri_shade, const float* pos, uint32_t num_vertices, uint32_t first,
                            uint32_t count, hipStream_t stream);

@@ -11,6 +11,7 @@
 // the GPU: both child boxes in the parent (64 B nodes), <= 4 triangles per leaf,
 // SAH splits, depth-capped so the LDS traversal stack has a hard bound.
 #include "scene_prep.h"
+#include "kernels/materials.h"
 
 #include <algorithm>
 #include <array>
@@ -598,6 +599,20 @@ gbl_status validate_meshes(const gbl_scene_desc& d, std::string* err) {
     return GBL_OK;
 }
 
+// The occupied texture slots of material i: in range, no cycle, no deeper than the device evaluates
+gbl_status validate_material_slots(const gbl_scene_desc& d, uint32_t i, std::string* err) {
+    for (int32_t t : texture_slots(d.materials[i])) {
+        if (t < 0) continue;
+        const int depth = texture_depth(d, t, 0);
+        if (depth < 0)
+            return refuse(GBL_ERR_INVALID, "material " + std::to_string(i) + " references a texture out of range (or a cyclic texture graph)", err);
+        if (depth > GBL_TEX_MAX_DEPTH)
+            return refuse(GBL_ERR_UNSUPPORTED, "material " + std::to_string(i) + ": texture graph deeper than " +
+                          std::to_string(GBL_TEX_MAX_DEPTH) + " levels below the material slot is outside the device path", err);
+    }
+    return GBL_OK;
+}
+
 gbl_status validate_materials(const gbl_scene_desc& d, std::string* err) {
     for (uint32_t i = 0; i < d.num_materials; ++i) {
         const gbl_material& m = d.materials[i];
@@ -605,15 +620,8 @@ gbl_status validate_materials(const gbl_scene_desc& d, std::string* err) {
         if (m.type == GBL_MAT_MASK && (m.masked_material < 0 || static_cast<uint32_t>(m.masked_material) >= d.num_materials ||
                                        d.materials[m.masked_material].type == GBL_MAT_MASK || d.materials[m.masked_material].type == GBL_MAT_SUBSURFACE))
             return refuse(GBL_ERR_INVALID, "mask material " + std::to_string(i) + " must wrap a non-mask, non-subsurface material of the scene", err);
-        for (int32_t t : texture_slots(m)) {
-            if (t < 0) continue;
-            const int depth = texture_depth(d, t, 0);
-            if (depth < 0)
-                return refuse(GBL_ERR_INVALID, "material " + std::to_string(i) + " references a texture out of range (or a cyclic texture graph)", err);
-            if (depth > GBL_TEX_MAX_DEPTH)
-                return refuse(GBL_ERR_UNSUPPORTED, "material " + std::to_string(i) + ": texture graph deeper than " +
-                              std::to_string(GBL_TEX_MAX_DEPTH) + " levels below the material slot is outside the device path", err);
-        }
+        const gbl_status st = validate_material_slots(d, i, err);
+        if (st != GBL_OK) return st;
     }
     return GBL_OK;
 }
@@ -990,43 +998,44 @@ gbl_status pack_instances(const gbl_scene_desc& d, PackedScene* out, Aabb* scene
 }
 
 // ------------------------------------------- materials, images and textures
+// One material's record: its type and slots, a mask's view of the material it wraps, then the editable fields (kernels/materials.h
+// mat_compose, which the device edit runs as well).  `all` is the description's whole list: a mask reads the one it wraps.
+void pack_material(const gbl_material* all, uint32_t i, DevMaterial* out) {
+    const gbl_material& m = all[i];
+    DevMaterial& dm = *out;
+    memset(&dm, 0, sizeof(dm));
+    dm.type = m.type;
+    dm.tex_color = m.tex_color;
+    dm.tex_color2 = m.tex_color2;
+    dm.tex_exponent = m.tex_exponent;
+    dm.has_tex = (m.tex_color >= 0 || m.tex_color2 >= 0 || m.tex_exponent >= 0) ? 1u : 0u;
+    dm.masked = m.type == GBL_MAT_MASK ? m.masked_material : -1;
+    dm.tex_color3 = -1;
+    // Material::perturb -> BumpShaders::evaluate; MaskMaterial::perturb forwards to the wrapped material (GoblinMaterial.h:456-458)
+    const gbl_material& bump_of = m.type == GBL_MAT_MASK ? all[m.masked_material] : m;
+    dm.tex_bump = bump_of.tex_bump;
+    dm.tex_normal = bump_of.tex_normal;
+    if (dm.tex_bump >= 0 || dm.tex_normal >= 0) dm.has_tex = 1u;
+    if (m.type == GBL_MAT_SUBSURFACE) {
+        dm.tex_color3 = m.tex_color3;
+        dm.has_tex = 1u;   // its fragments always carry dpdu / dpdv: BSSRDF::sampleProbeRay and MISWeight read them
+    }
+    if (m.type == GBL_MAT_MASK) {
+        const gbl_material& in = all[m.masked_material];
+        if (in.tex_color >= 0 || in.tex_color2 >= 0 || in.tex_exponent >= 0) dm.has_tex = 1u;
+    }
+    // colours, index, k, and the exponent: a subsurface material's is A of the BSSRDF ctor (GoblinMaterial.cpp:32-38)
+    float row[GBL_MAT_ROW_FLOATS];
+    mat_row_of(m, row);
+    mat_compose(&dm, row);
+}
+
 void pack_materials(const gbl_scene_desc& d, PackedScene* out) {
     out->materials.resize(d.num_materials);
     for (uint32_t i = 0; i < d.num_materials; ++i) {
         const gbl_material& m = d.materials[i];
-        DevMaterial& dm = out->materials[i];
-        memset(&dm, 0, sizeof(dm));
-        dm.type = m.type;
-        for (int k = 0; k < 3; ++k) dm.color[k] = m.color[k], dm.color2[k] = m.color2[k];
-        dm.index = m.index;
-        dm.k = m.k;
-        dm.exponent = m.exponent;
-        dm.tex_color = m.tex_color;
-        dm.tex_color2 = m.tex_color2;
-        dm.tex_exponent = m.tex_exponent;
-        dm.has_tex = (m.tex_color >= 0 || m.tex_color2 >= 0 || m.tex_exponent >= 0) ? 1u : 0u;
-        dm.masked = m.type == GBL_MAT_MASK ? m.masked_material : -1;
-        dm.tex_color3 = -1;
-        // Material::perturb -> BumpShaders::evaluate; MaskMaterial::perturb forwards to the wrapped material (GoblinMaterial.h:456-458)
-        const gbl_material& bump_of = m.type == GBL_MAT_MASK ? d.materials[m.masked_material] : m;
-        dm.tex_bump = bump_of.tex_bump;
-        dm.tex_normal = bump_of.tex_normal;
-        if (dm.tex_bump >= 0 || dm.tex_normal >= 0) dm.has_tex = 1u;
-        if (m.type == GBL_MAT_SUBSURFACE) {
-            for (int k = 0; k < 3; ++k) dm.color3[k] = m.color3[k];
-            dm.tex_color3 = m.tex_color3;
-            dm.has_tex = 1u;   // its fragments always carry dpdu / dpdv: BSSRDF::sampleProbeRay and MISWeight read them
-            // BSSRDF ctor (GoblinMaterial.cpp:32-38): A from the diffuse Fresnel reflectance polynomial (GoblinMaterial.h:94-105)
-            const float eta = m.index;
-            const float fdr = eta < 1.0f ? -0.4399f + 0.7099f / eta - 0.3319f / (eta * eta) + 0.0636f / (eta * eta * eta)
-                                         : -1.4399f / (eta * eta) + 0.7099f / eta + 0.6681f + 0.0636f * eta;
-            dm.exponent = (1.0f + fdr) / (1.0f - fdr);
-            out->has_bssrdf = out->extended = 1;
-        }
-        if (m.type == GBL_MAT_MASK) {
-            const gbl_material& in = d.materials[m.masked_material];
-            if (in.tex_color >= 0 || in.tex_color2 >= 0 || in.tex_exponent >= 0) dm.has_tex = 1u;
-        }
+        pack_material(d.materials, i, &out->materials[i]);
+        if (m.type == GBL_MAT_SUBSURFACE) out->has_bssrdf = out->extended = 1;
         for (int32_t t : texture_slots(m))
             if (t >= 0) out->extended = 1;
     }
@@ -1055,27 +1064,30 @@ void pack_images(const gbl_scene_desc& d, PackedScene* out) {
     }
 }
 
+// One texture's record: everything but value and the uv mapping, then those (kernels/materials.h tex_compose)
+void pack_texture(const gbl_texture& g, DevTexture* out) {
+    DevTexture& t = *out;
+    memset(&t, 0, sizeof(t));
+    t.type = g.type;
+    t.is_float = g.is_float;
+    t.child[0] = g.child[0], t.child[1] = g.child[1];
+    t.mapping = g.mapping;
+    t.filter = g.type == GBL_TEX_IMAGE ? g.image_filter : g.filter;
+    t.image = g.type == GBL_TEX_IMAGE ? g.image : -1;
+    t.address = g.address;
+    t.max_aniso = g.max_anisotropy;
+    if ((g.type == GBL_TEX_CHECKERBOARD || g.type == GBL_TEX_IMAGE) && g.mapping == GBL_MAP_SPHERICAL) {
+        Trs tt = compose(g.to_tex.position, g.to_tex.orientation, g.to_tex.scale);   // SphericalMapping::mToTex
+        store3x4(tt.m, t.to_tex);
+    }
+    float row[GBL_TEX_ROW_FLOATS];
+    tex_row_of(g, row);
+    tex_compose(&t, row);
+}
+
 void pack_textures(const gbl_scene_desc& d, PackedScene* out) {
     out->textures.resize(d.num_textures);
-    for (uint32_t i = 0; i < d.num_textures; ++i) {
-        const gbl_texture& g = d.textures[i];
-        DevTexture& t = out->textures[i];
-        memset(&t, 0, sizeof(t));
-        t.type = g.type;
-        t.is_float = g.is_float;
-        for (int k = 0; k < 3; ++k) t.value[k] = g.is_float ? g.value[0] : g.value[k];
-        t.child[0] = g.child[0], t.child[1] = g.child[1];
-        t.mapping = g.mapping;
-        t.filter = g.type == GBL_TEX_IMAGE ? g.image_filter : g.filter;
-        t.image = g.type == GBL_TEX_IMAGE ? g.image : -1;
-        t.address = g.address;
-        t.max_aniso = g.max_anisotropy;
-        for (int k = 0; k < 2; ++k) t.uv_scale[k] = g.uv_scale[k], t.uv_offset[k] = g.uv_offset[k];
-        if ((g.type == GBL_TEX_CHECKERBOARD || g.type == GBL_TEX_IMAGE) && g.mapping == GBL_MAP_SPHERICAL) {
-            Trs tt = compose(g.to_tex.position, g.to_tex.orientation, g.to_tex.scale);   // SphericalMapping::mToTex
-            store3x4(tt.m, t.to_tex);
-        }
-    }
+    for (uint32_t i = 0; i < d.num_textures; ++i) pack_texture(d.textures[i], &out->textures[i]);
 }
 
 // -------------------------------------------------------------------- lights
@@ -1498,6 +1510,34 @@ void repack_lights(const gbl_light* edited, uint32_t first, uint32_t count, cons
 
 // Validate, then pack: every refusal comes from validate_desc, before any table is built; of the packers only the TLAS step
 // returns a status (build_tlas keeps its check for gbl_update_instances) and after validation it cannot fail.
+void repack_materials(const gbl_material* all, uint32_t num, uint32_t first, uint32_t count, std::vector<DevMaterial>* records, std::vector<uint32_t>* touched) {
+    touched->clear();
+    for (uint32_t i = 0; i < num; ++i) {
+        const bool edited = i >= first && i - first < count;
+        const bool wraps = all[i].type == GBL_MAT_MASK && static_cast<uint32_t>(all[i].masked_material) >= first && static_cast<uint32_t>(all[i].masked_material) - first < count;
+        if (!edited && !wraps) continue;
+        pack_material(all, i, &(*records)[i]);
+        touched->push_back(i);
+    }
+}
+
+void repack_textures(const gbl_texture* edited, uint32_t first, uint32_t count, std::vector<DevTexture>* records) {
+    for (uint32_t i = 0; i < count; ++i) pack_texture(edited[i], &(*records)[first + i]);
+}
+
+gbl_status check_material_slots(const gbl_material* materials, uint32_t num_materials, const gbl_texture* textures, uint32_t num_textures, uint32_t first, uint32_t count,
+                                std::string* err) {
+    gbl_scene_desc d;
+    memset(&d, 0, sizeof(d));
+    d.materials = materials, d.num_materials = num_materials;
+    d.textures = textures, d.num_textures = num_textures;
+    for (uint32_t i = first; i < first + count; ++i) {
+        const gbl_status st = validate_material_slots(d, i, err);
+        if (st != GBL_OK) return st;
+    }
+    return GBL_OK;
+}
+
 gbl_status pack_scene(const gbl_scene_desc* desc, PackedScene* out, std::string* err, bool device_blas) {
     const gbl_status valid = validate_desc(desc, err);
     if (valid != GBL_OK) return valid;

@@ -102,6 +102,18 @@ void pack_light_distribution(const std::vector<float>& power, std::vector<float>
 void repack_lights(const gbl_light* edited, uint32_t first, uint32_t count, const float bound_lo[3], const float bound_hi[3], std::vector<DevLight>* lights,
                    std::vector<float>* power, std::vector<float>* cdf, std::vector<float>* pick_pdf);
 
+// A material's and a texture's record as pack_scene writes them, over a context's tables (gbl_update_materials,
+// gbl_update_textures).  `all` is the whole patched description of `num` materials: records [first, first + count) are packed
+// again, and so is every mask that wraps one of them (its record carries the wrapped material's has_tex, tex_bump and
+// tex_normal); *touched lists the records written, ascending.  The editable values go through kernels/materials.h's mat_compose /
+// tex_compose, which the device forms of the edits run as well.
+void repack_materials(const gbl_material* all, uint32_t num, uint32_t first, uint32_t count, std::vector<DevMaterial>* records, std::vector<uint32_t>* touched);
+void repack_textures(const gbl_texture* edited, uint32_t first, uint32_t count, std::vector<DevTexture>* records);
+// validate_desc's checks on the occupied texture slots of materials [first, first + count) of a patched description -- in range,
+// no cyclic graph, no deeper than GBL_TEX_MAX_DEPTH -- with its statuses and messages.
+gbl_status check_material_slots(const gbl_material* materials, uint32_t num_materials, const gbl_texture* textures, uint32_t num_textures, uint32_t first, uint32_t count,
+                                std::string* err);
+
 // What an image based light's tables take from the host besides its texels, stated once for pack_scene and for
 // gbl_update_environment: sin(theta) at the centre of each of the distribution's dist_h rows (ImageBasedLight's constructor,
 // with the loader's sinf), and the area 4 pi r^2 of the scene bound's sphere that its power is taken over.

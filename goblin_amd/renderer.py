@@ -358,6 +358,110 @@ class HipPathTracer:
             raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
         return {"records": records, "cdf": cdf, "pick_pdf": pick, "total": n}
 
+    _MATERIAL = np.dtype([("type", "<u4"), ("color", "<f4", 3), ("color2", "<f4", 3), ("index", "<f4"), ("k", "<f4"), ("exponent", "<f4"),
+                          ("tex_color", "<i4"), ("tex_color2", "<i4"), ("tex_exponent", "<i4"), ("has_tex", "<u4"), ("masked", "<i4"),
+                          ("color3", "<f4", 3), ("tex_color3", "<i4"), ("tex_bump", "<i4"), ("tex_normal", "<i4"), ("pad", "<f4")])
+    _TEXTURE = np.dtype([("type", "<u4"), ("is_float", "<u4"), ("value", "<f4", 3), ("child", "<i4", 2), ("mapping", "<u4"), ("filter", "<u4"),
+                         ("uv_scale", "<f4", 2), ("uv_offset", "<f4", 2), ("to_tex", "<f4", 12), ("image", "<i4"), ("address", "<u4"),
+                         ("max_aniso", "<f4"), ("pad", "<f4", 2)])
+    MATERIAL_ROW = 12   # floats of a device row: color[3], color2[3], color3[3], index, k, exponent
+    TEXTURE_ROW = 7     # value[3], uv_scale[2], uv_offset[2]
+
+    def _get_records(self, name, record, n):
+        arr = (record * max(n, 1))()
+        st = getattr(self.lib, name)(self.handle, 0, n, arr)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode() or name)
+        return [arr[i] for i in range(n)]
+
+    def materials(self):
+        """The material records the context holds now (gbl_get_materials): a list of gbl_material, the scene's at first, the
+        edited ones after ``update_materials``.  The first call after an edit from a tensor downloads what that edit wrote."""
+        return self._get_records("gbl_get_materials", _abi.gbl_material, int(self.scene.desc.num_materials))
+
+    def textures(self):
+        """The texture records the context holds now (gbl_get_textures), as ``materials``."""
+        return self._get_records("gbl_get_textures", _abi.gbl_texture, int(self.scene.desc.num_textures))
+
+    def _update_records(self, what, first, records, stream, fields, record, row, total, current, host_fn, device_fn):
+        torch = _torch()
+        first = int(first)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if isinstance(records, torch.Tensor):
+            if fields:
+                raise TypeError("%s: give a tensor of rows or keyword fields, not both" % what)
+            t = records
+            if t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.shape[1] != row or not t.is_contiguous():
+                raise ValueError("%s rows must be a contiguous float32 (n, %d) tensor on %s, got %s %s on %s%s" %
+                                 (what, row, self.device, t.dtype, tuple(t.shape), t.device, "" if t.is_contiguous() else ", not contiguous"))
+            if first < 0 or first + t.shape[0] > total:
+                raise ValueError("%s %d .. %d out of range: the scene holds %d" % (what, first, first + t.shape[0], total))
+            if t.shape[0] == 0:
+                return
+            st = getattr(self.lib, device_fn)(self.handle, first, t.shape[0], t.data_ptr(), s.cuda_stream)
+        else:
+            if records is not None and fields:
+                raise TypeError("%s: give records or keyword fields, not both" % what)
+            if records is None:
+                names = {name for name, _ in record._fields_}
+                for name in fields:
+                    if name not in names:
+                        raise TypeError("%s has no field %r" % (record.__name__, name))
+                if not 0 <= first < total and fields:
+                    raise ValueError("%s %d out of range: the scene holds %d" % (what, first, total))
+                rec = current()[first] if fields else None
+                for name, value in fields.items():
+                    if name == "to_tex" and not isinstance(value, _abi.gbl_trs):
+                        for part, values in zip(("position", "orientation", "scale"), value):
+                            getattr(rec.to_tex, part)[:] = [float(v) for v in values]
+                    elif isinstance(getattr(rec, name), C.Array):
+                        getattr(rec, name)[:] = [float(v) for v in value]
+                    else:
+                        setattr(rec, name, value)
+                records = [rec] if fields else []
+            records = list(records)
+            for r in records:
+                if not isinstance(r, record):
+                    raise TypeError("%s records must be %s, got %s" % (what, record.__name__, type(r).__name__))
+            if first < 0 or first + len(records) > total:
+                raise ValueError("%s %d .. %d out of range: the scene holds %d" % (what, first, first + len(records), total))
+            arr = (record * max(len(records), 1))(*records)
+            st = getattr(self.lib, host_fn)(self.handle, first, len(records), arr, s.cuda_stream)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+
+    def update_materials(self, first, materials=None, stream=None, **fields):
+        """Edit materials (gbl_update_materials).  ``materials``: gbl_material records for materials first..; without it, material
+        ``first`` takes the named gbl_material fields -- color, color2, color3 (3 floats each), index, k, exponent, and the texture
+        index of an occupied slot -- and what is not given keeps its value.  type, masked_material and whether a slot is occupied
+        cannot change.  A contiguous float32 (n, 12) torch tensor on the tracer's device -- rows of color, color2, color3, index,
+        k, exponent -- is read where it lies by a kernel (gbl_update_materials_device; a slice with a storage offset is fine,
+        and its values are not inspected); any other tensor is a ValueError.  Queued on ``stream`` (a torch stream; the current
+        one by default) without a synchronisation."""
+        self._update_records("material", first, materials, stream, fields, _abi.gbl_material, self.MATERIAL_ROW, int(self.scene.desc.num_materials),
+                             self.materials, "gbl_update_materials", "gbl_update_materials_device")
+
+    def update_textures(self, first, textures=None, stream=None, **fields):
+        """Edit nodes of the texture graph (gbl_update_textures).  ``textures``: gbl_texture records for textures first..; without
+        it, texture ``first`` takes the named fields -- value (3 floats), uv_scale, uv_offset (2 each), to_tex (a (position,
+        orientation wxyz, scale) tuple or a gbl_trs), max_anisotropy.  Every other field cannot change.  A contiguous float32
+        (n, 7) torch tensor on the tracer's device -- rows of value, uv_scale, uv_offset -- takes the device form
+        (gbl_update_textures_device), as in ``update_materials``."""
+        self._update_records("texture", first, textures, stream, fields, _abi.gbl_texture, self.TEXTURE_ROW, int(self.scene.desc.num_textures),
+                             self.textures, "gbl_update_textures", "gbl_update_textures_device")
+
+    def _materials_raw(self):
+        """The device's material and texture records read back (gbl_selftest_materials): a dict of two numpy structured arrays.
+        For tests."""
+        nm, nt = C.c_uint64(), C.c_uint64()
+        st = self.lib.gbl_selftest_materials(self.handle, None, None, C.byref(nm), C.byref(nt))
+        if st == _abi.GBL_OK:
+            materials, textures = np.zeros(nm.value, self._MATERIAL), np.zeros(nt.value, self._TEXTURE)
+            st = self.lib.gbl_selftest_materials(self.handle, materials.ctypes.data, textures.ctypes.data, None, None)
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return {"materials": materials, "textures": textures}
+
     def _image_record(self, image):
         d = self.scene.desc
         if not 0 <= int(image) < d.num_images:

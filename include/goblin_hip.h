@@ -924,6 +924,68 @@ gbl_status gbl_get_lights(const gbl_ctx* ctx, uint32_t first, uint32_t count, gb
  * Synchronises the device when it copies. */
 gbl_status gbl_selftest_lights(gbl_ctx* ctx, void* records_out, float* cdf_out, float* pick_pdf_out, uint64_t* total);
 
+/* Material edit: materials [first, first + count) take the given records (host memory); the texture edit below does the same for
+ * the nodes of the texture graph.  These replace what the reference can only do by loading the scene again: createLambertMaterial
+ * .. createSubsurfaceMaterial (GoblinMaterial.cpp:826-927) and the texture creators (GoblinTexture.cpp:617-745) run once, when the
+ * scene file is read.  After GBL_OK and in stream order the material and texture records on the device are byte for byte what
+ * gbl_create packs from the context's current description with those records replaced, and every render, AOV pass and query
+ * queued afterwards equals the same call on such a fresh context, bit for bit.
+ *  - What may change in a material: color, color2, color3, index, k, exponent (by type as gbl_material lists them: a mask's alpha
+ *    and transparent colour, a subsurface material's sigma_a, sigma_s', Kr, eta and g among them; the "Kd" + "mean_free_path" form
+ *    stays the loader's), and the texture index held in an OCCUPIED slot.  What may not: type, masked_material, and whether each
+ *    of the six slots (tex_color, tex_color2, tex_exponent, tex_color3, tex_bump, tex_normal) is occupied (>= 0) or not (-1):
+ *    these decide DevInstance::is_mask, has_masks, has_bssrdf and the choice between the lean and the EXT kernels.
+ *  - What may change in a texture: value, uv_scale, uv_offset, to_tex, max_anisotropy.  What may not: type, is_float, child,
+ *    mapping, image, filter, image_filter, address.
+ *  - A mask's device record carries the slot state of the material it wraps: an edit of the wrapped material packs those masks
+ *    again as well.
+ *  - The records are packed on the host and their uploads are queued on `stream` (a hipStream_t, NULL for the null stream) from
+ *    pinned staging the context owns.  No kernel is launched and the device is not synchronised: work queued on that stream
+ *    before the call keeps the old values, work queued after it sees the new ones.  A caller who renders on another stream orders
+ *    the two itself.  The staging has four slots per table; a fifth edit waits for the first one's upload.  (One exception: the
+ *    first host-form edit or gbl_get_* after a device-form edit downloads the rows that edit wrote, behind a synchronise.)
+ *  - gbl_film_accumulate keeps its history across the edit, as across a light edit.  GBL_SCHEDULE_AUTO measures its rays per
+ *    path again.
+ * Refusals, in this order, nothing uploaded and the context untouched: GBL_ERR_INVALID for a NULL ctx or pointer; GBL_ERR_INVALID
+ * for a range past the context's records; per record GBL_ERR_INVALID for a fixed field that is not the context's, naming the
+ * record, the field and both values; per record GBL_ERR_INVALID for an editable float that is not finite (color3 counts in a
+ * subsurface material only), naming the field, and for a spherical checkerboard's or image texture's to_tex that the reference
+ * cannot invert (|det| < 1e-5, pack_transform's refusal); then for a slot that names another texture GBL_ERR_INVALID for a
+ * texture of the other kind (tex_exponent and tex_bump take float textures, the others colour textures), and validate_desc's
+ * refusals on the patched table: GBL_ERR_INVALID for an index out of range or a cyclic graph, GBL_ERR_UNSUPPORTED for a graph
+ * deeper than GBL_TEX_MAX_DEPTH below the slot.  count == 0 with a valid pointer is GBL_OK and changes nothing. */
+gbl_status gbl_update_materials(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_material* materials /* host */, void* stream);
+gbl_status gbl_update_textures(gbl_ctx* ctx, uint32_t first, uint32_t count, const gbl_texture* textures /* host */, void* stream);
+/* The records the context holds now: gbl_create's at first, the edited ones after.  Host only, but for the first call after a
+ * device-form edit, which downloads the rows that edit wrote once (it synchronises the device).  GBL_ERR_INVALID for a NULL
+ * argument or a range out of bounds. */
+gbl_status gbl_get_materials(gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_material* out /* host */);
+gbl_status gbl_get_textures(gbl_ctx* ctx, uint32_t first, uint32_t count, gbl_texture* out /* host */);
+/* The same edits with the editable floats read from DEVICE memory: what an optimiser or an animation step on the GPU leaves
+ * behind goes into the context without a trip through the host (the constructors cited above, again).  d_rows holds `count` rows,
+ * 4-byte aligned: a material row is 12 floats {color[3], color2[3], color3[3], index, k, exponent}, a texture row 7 floats
+ * {value[3], uv_scale[2], uv_offset[2]}; slot indices, to_tex and max_anisotropy stay with the host forms.  One kernel with one
+ * lane per record reads the live record, keeps every fixed field and writes the editable ones with the packer's own arithmetic:
+ * after the call and in stream order the records are byte for byte what gbl_update_materials / gbl_update_textures leave when
+ * fed the same floats -- color3 stays zero outside a subsurface material, a float texture's value[0] is broadcast, a subsurface
+ * material's A is worked out from index (BSSRDF ctor, GoblinMaterial.cpp:32-38) and its row's exponent is ignored.
+ *  - Asynchronous on `stream`, nothing is synchronised.  The VALUES ARE NOT INSPECTED: a NaN or an infinity in a row goes into
+ *    the record as it is, as gbl_update_image_device does not look at texels and gbl_create does not look at material values.
+ *  - The context's host copy becomes a mirror: the edit marks its range stale, and gbl_get_materials / gbl_get_textures and the
+ *    host forms refresh it with one download of the union of the stale ranges, behind a synchronise, when they need it.  The raw
+ *    rows are kept in a device table made from the host copy at the first device-form edit (which allocates, and uploads it on
+ *    `stream`) and written by every edit of either form after that.
+ * Refusals, nothing launched and the context untouched: GBL_ERR_INVALID for a NULL ctx or pointer, a range past the context's
+ * records, a pointer that is not device or managed memory of the context's device (a plain host pointer is refused before
+ * anything reads it), an allocation that ends before the rows' bytes. */
+gbl_status gbl_update_materials_device(gbl_ctx* ctx, uint32_t first, uint32_t count, const float* d_rows /* device, 12 * count */, void* stream);
+gbl_status gbl_update_textures_device(gbl_ctx* ctx, uint32_t first, uint32_t count, const float* d_rows /* device, 7 * count */, void* stream);
+/* Self-test hook: every DevMaterial record (88 B: type, color[3], color2[3], index, k, exponent, tex_color, tex_color2,
+ * tex_exponent, has_tex, masked, color3[3], tex_color3, tex_bump, tex_normal, pad) and every DevTexture record (120 B: type,
+ * is_float, value[3], child[2], mapping, filter, uv_scale[2], uv_offset[2], to_tex[12], image, address, max_aniso, pad[2]) to
+ * host memory, and the two counts.  Any out pointer may be NULL.  Synchronises the device when it copies. */
+gbl_status gbl_selftest_materials(gbl_ctx* ctx, void* materials_out, void* textures_out, uint64_t* num_materials, uint64_t* num_textures);
+
 /* Image edit: image `image` of gbl_scene_desc.images takes a new level 0 and the MIP levels above it are built again on the
  * device.  level0 holds width * height * channels floats in level 0's layout as the context holds that image -- what the loader
  * leaves behind: texels already through ImageTexture::convertTexel (channel pick and gamma done), sides already powers of two, a
