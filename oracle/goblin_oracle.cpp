@@ -1716,6 +1716,59 @@ inline int material_type_bits(const gbl_material& m) {
         default: return BSDF_DIFFUSE | BSDF_REFLECTION;
     }
 }
+// What the surface probe notes about one camera sample (test infrastructure, tests/test_surface_chart_cpu.py): one bit per
+// event, counted over every vertex of the sample's path (Whitted: every level, every light) and kept as a bit mask for the first
+// vertex; the first vertex's material, picked light, reflectChance and maskedProb.  The functions below note into it through a
+// thread-local pointer that only orc_surface sets: they read what they computed and change none of it.
+enum {
+    SURF_ENTERING = 0, SURF_LEAVING = 1,            // a transparent vertex met from outside / from inside (specularRefract's coso > 0)
+    SURF_TOTAL_REFLECTION = 2,                      // ... whose Fresnel term is 1: specularRefract's `f == 1.0f`
+    SURF_REFLECT = 3, SURF_REFRACT = 4,             // the lobe `uComponent < reflectChance` chose
+    SURF_PUNCHED = 5,                               // a mask's BSDFnullptr lobe was sampled
+    SURF_BSDF_BLACK = 6,                            // the BSDF's value towards a usable light sample is black
+    SURF_SAMPLE_BLACK = 7, SURF_SAMPLE_PDF_ZERO = 8,   // sampleBSDF returned black / a pdf of 0
+    SURF_LIGHT_BLACK = 9, SURF_LIGHT_PDF_ZERO = 10,    // sampleL returned black / a pdf of 0
+    SURF_OCCLUDED = 11, SURF_UNOCCLUDED = 12, SURF_ATTENUATED = 13,   // the shadow ray; attenuated: unoccluded through a mask
+    SURF_SPOT_OUTSIDE = 14, SURF_SPOT_FALLOFF = 15, SURF_SPOT_FULL = 16,
+    SURF_EMITTER_BACK = 17,                         // AreaLight::L / Intersection::Le asked from behind (or edge-on)
+    SURF_SPHERE_INSIDE = 18,                        // Sphere::sample's `< 1e-4f` uniform branch
+    SURF_END_PICKED = 19, SURF_END_OTHER = 20, SURF_END_SURFACE = 21, SURF_END_ESCAPED = 22,   // where the BSDF-sampled ray ended
+    SURF_ENV_ADDED = 23,                            // ... escaped, and environment radiance that is not black was added
+    SURF_BITS = 24,
+    SURF_MATERIAL = 0,        // the first vertex's material type + 1 (0: the camera ray escaped), + 16 under a mask
+    SURF_REFLECT_CHANCE = 1,  // the first transparent vertex's reflectChance
+    SURF_MASKED_PROB = 2,     // the first masked vertex's maskedProb
+    SURF_LIGHT = 3,           // the light picked at the first vertex + 1 (path tracer)
+    SURF_FIRST = 4,           // the first vertex's events, a bit mask
+    SURF_VERTICES = 5, SURF_NAN = 6,
+    SURF_EARLY_ESCAPE = 7,    // paths that only punched through masks and then escaped: the `firstBounce` rule adds the environment
+    SURF_LATE_ESCAPE = 8,     // punched-through paths that escaped after a bounce that was not a punch: no environment is added
+    SURF_INSIDE_EPSILON = 9,  // light samples nearer than the fragment's epsilon: the shadow ray's maxt = dist - epsilon is negative
+    SURF_COUNTS = 10,         // + event: the number of times it was noted
+    SURF_PROBE_WORDS = SURF_COUNTS + SURF_BITS
+};
+struct SurfProbe {
+    float w[SURF_PROBE_WORDS] = {};
+    uint32_t first = 0;
+    int vertex = 0;           // the vertex under way (path tracer: the bounce; Whitted: the recursion level)
+    bool have_chance = false, have_masked = false;
+};
+static thread_local SurfProbe* g_surf = nullptr;
+inline void surf_note(int event) {
+    if (!g_surf) return;
+    g_surf->w[SURF_COUNTS + event] += 1.0f;
+    if (g_surf->vertex == 0) g_surf->first |= 1u << event;
+}
+inline void surf_vertex(int vertex, int material_type, bool is_mask, int light) {
+    if (!g_surf) return;
+    g_surf->vertex = vertex;
+    g_surf->w[SURF_VERTICES] += 1.0f;
+    if (vertex == 0 && g_surf->w[SURF_MATERIAL] == 0.0f) {
+        g_surf->w[SURF_MATERIAL] = static_cast<float>(material_type + 1 + (is_mask ? 16 : 0));
+        g_surf->w[SURF_LIGHT] = static_cast<float>(light + 1);
+    }
+}
+
 inline bool match_type(int type, int to_match) { return (type & to_match) == to_match; }
 inline int sample_type(V3 wo, V3 wi, V3 n, int type) {   // Material::getSampleType, :285-294
     if (dot(n, wo) * dot(n, wi) > 0.0f) return type & ~BSDF_TRANSMISSION;
@@ -1764,13 +1817,17 @@ float specular_reflect_conductor(V3 n, V3 wo, V3* wi, float eta, float k) {   //
 float specular_refract(V3 n, V3 wo, V3* wi, float etao, float etai) {   // :343-387, radiance mode
     float coso = dot(n, wo);
     float et = etao, ei = etai;
+    surf_note(coso > 0.0f ? SURF_ENTERING : SURF_LEAVING);
     if (!(coso > 0.0f)) {
         std::swap(ei, et);
         n = -n;
         coso = -coso;
     }
     float f = fresnel_dielectric(coso, et, ei);
-    if (f == 1.0f) return 0.0f;
+    if (f == 1.0f) {
+        surf_note(SURF_TOTAL_REFLECTION);
+        return 0.0f;
+    }
     float eta = et / ei;
     *wi = normalize(n * (eta * coso - std::sqrt(std::max(0.0f, 1.0f - eta * eta * (1.0f - coso * coso)))) - eta * wo);
     return eta * eta * (1.0f - f) / absdot(*wi, n);
@@ -1853,12 +1910,18 @@ Col mat_sample(const gbl_material& m, const Frag& frag, V3 wo, float u_comp, flo
             float refract = specular_refract(n, wo, &w_refr, 1.0f, m.index);
             float fresnel = reflect * absdot(w_refl, n);
             float chance = fresnel;
+            if (g_surf && !g_surf->have_chance) {
+                g_surf->have_chance = true;
+                g_surf->w[SURF_REFLECT_CHANCE] = chance;
+            }
             if (u_comp < chance) {
+                surf_note(SURF_REFLECT);
                 *wi = w_refl;
                 *sampled = BSDF_SPECULAR | BSDF_REFLECTION;
                 *pdf = chance;
                 return mat_color(m) * reflect;
             }
+            surf_note(SURF_REFRACT);
             *wi = w_refr;
             *sampled = BSDF_SPECULAR | BSDF_TRANSMISSION;
             *pdf = 1.0f - chance;
@@ -1896,11 +1959,16 @@ float rmat_pdf(const ResolvedMat& r, V3 n, V3 wo, V3 wi) {
 Col rmat_sample(const ResolvedMat& r, const Frag& frag, V3 wo, float u_comp, float u1, float u2, V3* wi, float* pdf, int* sampled) {
     if (!r.is_mask) return mat_sample(r.m, frag, wo, u_comp, u1, u2, wi, pdf, sampled);
     float masked_prob = r.alpha;
+    if (g_surf && !g_surf->have_masked) {
+        g_surf->have_masked = true;
+        g_surf->w[SURF_MASKED_PROB] = masked_prob;
+    }
     if (u_comp < masked_prob) {
         Col result = r.alpha * mat_sample(r.m, frag, wo, u_comp, u1, u2, wi, pdf, sampled);
         *pdf *= masked_prob;
         return result;
     }
+    surf_note(SURF_PUNCHED);
     Col result = (1.0f - r.alpha) * r.tcolor;
     *wi = -normalize(wo);
     *pdf = 1.0f - masked_prob;
@@ -1910,8 +1978,15 @@ Col rmat_sample(const ResolvedMat& r, const Frag& frag, V3 wo, float u_comp, flo
 
 float spot_falloff(const Light& l, V3 w) {   // :277-287
     float cos_t = dot(w, l.spot_axis);
-    if (cos_t < l.cos_max) return 0.0f;
-    if (cos_t > l.cos_falloff) return 1.0f;
+    if (cos_t < l.cos_max) {
+        surf_note(SURF_SPOT_OUTSIDE);
+        return 0.0f;
+    }
+    if (cos_t > l.cos_falloff) {
+        surf_note(SURF_SPOT_FULL);
+        return 1.0f;
+    }
+    surf_note(SURF_SPOT_FALLOFF);
     float d = (cos_t - l.cos_max) / (l.cos_falloff - l.cos_max);
     return d * d * d * d;
 }
@@ -1975,6 +2050,7 @@ V3 shape_sample(const Mesh& m, V3 p, float u1, float u2, V3* normal) {
     float r2 = m.radius * m.radius;
     float d2 = sqlen(p);
     if (d2 - r2 < 1e-4f) {
+        surf_note(SURF_SPHERE_INSIDE);
         *normal = uniform_sample_sphere(u1, u2);
         return m.radius * (*normal);
     }
@@ -2043,7 +2119,9 @@ Col light_sample(const orc_scene* s, int li, V3 p, float epsilon, float u_comp, 
         shadow->d = *wi;
         shadow->mint = epsilon;
         shadow->maxt = length(ps - p) - epsilon;
-        return dot(ns, -*wi) > 0.0f ? l.color : BLACK;   // AreaLight::L, :368-371
+        if (dot(ns, -*wi) > 0.0f) return l.color;   // AreaLight::L, :368-371
+        surf_note(SURF_EMITTER_BACK);
+        return BLACK;
     }
     if (l.type == GBL_LIGHT_IBL) {   // ImageBasedLight::sampleL, :529-555
         float pdf_row, pdf_col;
@@ -2130,7 +2208,30 @@ Col environment_le(const orc_scene* s, V3 dir) {
 Col hit_Le(const orc_scene* s, const Hit& h, V3 out_dir) {
     int al = s->instances[h.instance].area_light;
     if (al < 0) return BLACK;
-    return dot(h.frag.n, out_dir) > 0.0f ? s->lights[al].color : BLACK;
+    if (dot(h.frag.n, out_dir) > 0.0f) return s->lights[al].color;
+    surf_note(SURF_EMITTER_BACK);
+    return BLACK;
+}
+
+// the surface probe's notes on a light sample, a BSDF sample and the end of the BSDF-sampled ray (nothing without the probe)
+inline void surf_light_sample(Col L, float pdf, const Ray& shadow) {
+    if (g_surf && shadow.maxt < 0.0f) g_surf->w[SURF_INSIDE_EPSILON] += 1.0f;
+    if (L == BLACK) surf_note(SURF_LIGHT_BLACK);
+    if (!(pdf > 0.0f)) surf_note(SURF_LIGHT_PDF_ZERO);
+}
+inline void surf_bsdf_sample(Col f, float pdf) {
+    if (f == BLACK) surf_note(SURF_SAMPLE_BLACK);
+    if (!(pdf > 0.0f)) surf_note(SURF_SAMPLE_PDF_ZERO);
+}
+inline void surf_end(const orc_scene* s, bool hit, const Hit& h, int light, V3 dir) {
+    if (!g_surf) return;
+    if (!hit) {
+        surf_note(SURF_END_ESCAPED);
+        if (light_le_escaped(s, light, dir) != BLACK) surf_note(SURF_ENV_ADDED);
+        return;
+    }
+    const int al = s->instances[h.instance].area_light;
+    surf_note(al == light ? SURF_END_PICKED : al >= 0 ? SURF_END_OTHER : SURF_END_SURFACE);
 }
 
 // ---------------------------------------------------------------------------
@@ -2834,6 +2935,7 @@ Col path_li(LiCtx* c, const Ray& primary, const float* rec, const RayDiff* prima
         Col Ld(0.0f);
         compute_uv_differential(&hit.frag, bounce == 0 ? primary_diff : nullptr);   // :77; only the camera ray has differentials
         const ResolvedMat mat = resolve_hit_material(s, s->instances[hit.instance].material, hit.frag);
+        surf_vertex(bounce, mat.m.type, mat.is_mask, light);
         const Frag& frag = hit.frag;
         V3 wo = -cur.d;
         V3 wi;
@@ -2841,11 +2943,16 @@ Col path_li(LiCtx* c, const Ray& primary, const float* rec, const RayDiff* prima
         float light_pdf_v, bsdf_pdf;
         Ray shadow;
         Col L = light_sample(s, light, p, epsilon, ls_comp, ls_geo[0], ls_geo[1], &wi, &light_pdf_v, &shadow);
+        surf_light_sample(L, light_pdf_v, shadow);
         if (L != BLACK && light_pdf_v > 0.0f) {
             Col f = rmat_bsdf(mat, n, wo, wi);
-            if (f != BLACK && !scene_occluded(s, shadow, &c->cnt, FILTER_OPAQUE)) {
+            if (f == BLACK) surf_note(SURF_BSDF_BLACK);
+            const bool occluded = f != BLACK && scene_occluded(s, shadow, &c->cnt, FILTER_OPAQUE);
+            if (f != BLACK) surf_note(occluded ? SURF_OCCLUDED : SURF_UNOCCLUDED);
+            if (f != BLACK && !occluded) {
                 draw_bsdf_sample(c);
                 Col tr = eval_attenuation(c, shadow);
+                if (tr.r != 1.0f || tr.g != 1.0f || tr.b != 1.0f) surf_note(SURF_ATTENUATED);
                 if (light_is_delta(s->lights[light])) {
                     Ld += f * tr * L * absdot(n, wi) / light_pdf_v;
                 } else {
@@ -2857,6 +2964,7 @@ Col path_li(LiCtx* c, const Ray& primary, const float* rec, const RayDiff* prima
         }
         int sampled = 0;
         Col f = rmat_sample(mat, frag, wo, bs_comp, bs_dir[0], bs_dir[1], &wi, &bsdf_pdf, &sampled);
+        surf_bsdf_sample(f, bsdf_pdf);
         if (f != BLACK && bsdf_pdf > 0.0f) {
             if (sampled == BSDF_NULL) {
                 // stepped on an index-matched (mask) BSDF: punch through, no direct light for this bounce (:122-136)
@@ -2867,6 +2975,9 @@ Col path_li(LiCtx* c, const Ray& primary, const float* rec, const RayDiff* prima
                 if (!scene_intersect(s, cur, &nh, &c->cnt)) {
                     // "primary ray need to evaluate image based lighting in this case" (:125-131)
                     if (first_bounce) Li += throughput * environment_le(s, cur.d);
+                    surf_note(SURF_END_ESCAPED);
+                    if (g_surf) g_surf->w[first_bounce ? SURF_EARLY_ESCAPE : SURF_LATE_ESCAPE] += 1.0f;
+                    if (g_surf && first_bounce && environment_le(s, cur.d) != BLACK) surf_note(SURF_ENV_ADDED);
                     break;
                 }
                 hit = nh;
@@ -2895,6 +3006,7 @@ Col path_li(LiCtx* c, const Ray& primary, const float* rec, const RayDiff* prima
                 bool lhit = scene_intersect(s, rr, &lh, &c->cnt, FILTER_OPAQUE);
                 draw_bsdf_sample(c);
                 Col tr = eval_attenuation(c, rr);
+                surf_end(s, lhit, lh, light, r.d);
                 if (lhit && s->instances[lh.instance].area_light == light) {
                     Col Le = hit_Le(s, lh, -wi);
                     if (Le != BLACK) Ld += f * tr * Le * absdot(wi, n) * fw / bsdf_pdf;
@@ -2916,6 +3028,7 @@ Col path_li(LiCtx* c, const Ray& primary, const float* rec, const RayDiff* prima
             lh.frag = hit.frag;
             Ray rr = r;
             bool lhit = scene_intersect(s, rr, &lh, &c->cnt);
+            surf_end(s, lhit, lh, light, r.d);
             if (lhit) {
                 draw_bsdf_sample(c);
                 Col tr = eval_attenuation(c, r);
@@ -3002,9 +3115,13 @@ Col estimate_ld(LiCtx* c, V3 wo, float epsilon, const Hit& hit, const ResolvedMa
     float light_pdf_v, bsdf_pdf;
     Ray shadow;
     Col L = light_sample(s, light, p, epsilon, ls_comp, ls_geo[0], ls_geo[1], &wi, &light_pdf_v, &shadow);
+    surf_light_sample(L, light_pdf_v, shadow);
     if (L != BLACK && light_pdf_v > 0.0f) {
         Col f = rmat_bsdf(mat, n, wo, wi);
-        if (f != BLACK && !scene_occluded(s, shadow, &c->cnt)) {
+        if (f == BLACK) surf_note(SURF_BSDF_BLACK);
+        const bool occluded = f != BLACK && scene_occluded(s, shadow, &c->cnt);
+        if (f != BLACK) surf_note(occluded ? SURF_OCCLUDED : SURF_UNOCCLUDED);
+        if (f != BLACK && !occluded) {
             if (light_is_delta(s->lights[light])) return f * L * absdot(n, wi) / light_pdf_v;
             bsdf_pdf = rmat_pdf(mat, n, wo, wi);
             float lw = power_heuristic(1, light_pdf_v, 1, bsdf_pdf);
@@ -3018,6 +3135,7 @@ Col estimate_ld(LiCtx* c, V3 wo, float epsilon, const Hit& hit, const ResolvedMa
     if (mat_is_specular(mat.m) && !(mat.is_mask && !(bs_comp < mat.alpha))) return Ld;
     int sampled = 0;
     Col f = rmat_sample(mat, frag, wo, bs_comp, bs_dir[0], bs_dir[1], &wi, &bsdf_pdf, &sampled);
+    surf_bsdf_sample(f, bsdf_pdf);
     if (f != BLACK && bsdf_pdf > 0.0f) {
         float fw = 1.0f;
         if (!(sampled & BSDF_SPECULAR)) {
@@ -3029,7 +3147,9 @@ Col estimate_ld(LiCtx* c, V3 wo, float epsilon, const Hit& hit, const ResolvedMa
         r.o = p; r.d = wi; r.mint = epsilon; r.maxt = INF;
         Hit lh;
         lh.frag = hit.frag;
-        if (scene_intersect(s, r, &lh, &c->cnt)) {
+        const bool lhit = scene_intersect(s, r, &lh, &c->cnt);
+        surf_end(s, lhit, lh, light, r.d);
+        if (lhit) {
             if (s->instances[lh.instance].area_light == light) {
                 Col Le = hit_Le(s, lh, -wi);
                 if (Le != BLACK) Ld += f * Le * absdot(wi, n) * fw / bsdf_pdf;
@@ -3086,6 +3206,7 @@ Col whitted_li(LiCtx* c, const Ray& ray_in, const float* rec, const RayDiff* dif
     c->sss_level = depth;
     Li += l_subsurface(c, hit, -ray.d, rec);
     const ResolvedMat mat = resolve_hit_material(s, s->instances[hit.instance].material, hit.frag);
+    surf_vertex(depth, mat.m.type, mat.is_mask, -1);
     Li += multi_sample_ld(c, ray, hit.epsilon, hit, mat, rec);
     if (depth < c->rs->max_ray_depth) {
         const Frag& frag = hit.frag;
@@ -3094,6 +3215,7 @@ Col whitted_li(LiCtx* c, const Ray& ray_in, const float* rec, const RayDiff* dif
         {
             Col L(BLACK);
             draw_bsdf_sample(c);
+            if (g_surf) g_surf->vertex = depth;   // a child evaluation moved it
             V3 wi(0, 0, 0);
             float pdf = 0.0f;
             Col f(BLACK);
@@ -3119,6 +3241,7 @@ Col whitted_li(LiCtx* c, const Ray& ray_in, const float* rec, const RayDiff* dif
         {
             Col L(BLACK);
             draw_bsdf_sample(c);
+            if (g_surf) g_surf->vertex = depth;   // a child evaluation moved it
             V3 wi(0, 0, 0);
             float pdf = 0.0f;
             Col f(BLACK);
@@ -3787,6 +3910,30 @@ int32_t orc_subsurface(const orc_scene* s, const gbl_render_setting* rs, const f
         probe.w[SSS_LIGHTS] = static_cast<float>(probe.lights);
         probe.w[SSS_NAN] = static_cast<float>(probe.nan);
         memcpy(out + SSS_PROBE_WORDS * i, probe.w, sizeof(probe.w));
+        if (li_out) { li_out[4 * i] = L.r; li_out[4 * i + 1] = L.g; li_out[4 * i + 2] = L.b; li_out[4 * i + 3] = L.a; }
+    }
+    return 0;
+}
+
+// The surface probe: per record SURF_PROBE_WORDS floats (the SURF_* words above) noted by the very material, light and
+// integrator functions that orc_li_replay and orc_render evaluate, under the record's own draws; li_out (optional) receives
+// what orc_li_replay gives.
+int32_t orc_surface(const orc_scene* s, const gbl_render_setting* rs, const float* samples, int64_t n, float* out, float* li_out) {
+    if (!s || !rs || !samples || !out) return -1;
+    PtIndices ix;
+    Quota q = make_quota(*rs, &ix, s);
+    const uint32_t dims = q.dims();
+    LiCtx c;
+    c.s = s; c.rs = rs; c.q = &q; c.ix = &ix; c.rng = nullptr; c.ref_faithful = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        SurfProbe probe;
+        g_surf = &probe;
+        Col L = eval_li(&c, samples + i * dims);
+        g_surf = nullptr;
+        if (s->volume.on) L = task_sample(&c, samples + i * dims, L);
+        probe.w[SURF_FIRST] = static_cast<float>(probe.first);
+        probe.w[SURF_NAN] = (std::isnan(L.r) || std::isnan(L.g) || std::isnan(L.b)) ? 1.0f : 0.0f;
+        memcpy(out + SURF_PROBE_WORDS * i, probe.w, sizeof(probe.w));
         if (li_out) { li_out[4 * i] = L.r; li_out[4 * i + 1] = L.g; li_out[4 * i + 2] = L.b; li_out[4 * i + 3] = L.a; }
     }
     return 0;

@@ -80,6 +80,8 @@ def lib():
         L.orc_subsurface.restype = C.c_int32
         L.orc_sss_offsets.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.POINTER(C.c_int32)]
         L.orc_sss_offsets.restype = None
+        L.orc_surface.argtypes = [C.c_void_p, C.POINTER(_abi.gbl_render_setting), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.orc_surface.restype = C.c_int32
         L.orc_hardware_threads.restype = C.c_int32
         L.orc_mip_lookup.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
         L.orc_mip_lookup.restype = C.c_int32
@@ -230,6 +232,28 @@ class Oracle:
         out, li = np.zeros((samples.shape[0], self.SSS_WORDS), np.float32), np.zeros((samples.shape[0], 4), np.float32)
         if lib().orc_subsurface(self.h, C.byref(s), _ptr(samples), samples.shape[0], _ptr(out), _ptr(li)) != 0:
             raise RuntimeError("orc_subsurface failed")
+        return out, li
+
+    # the surface probe's events (a bit of word SURF_FIRST, a counter at SURF_COUNTS + event) and words
+    SURF_EVENTS = ("ENTERING", "LEAVING", "TOTAL_REFLECTION", "REFLECT", "REFRACT", "PUNCHED", "BSDF_BLACK", "SAMPLE_BLACK", "SAMPLE_PDF_ZERO",
+                   "LIGHT_BLACK", "LIGHT_PDF_ZERO", "OCCLUDED", "UNOCCLUDED", "ATTENUATED", "SPOT_OUTSIDE", "SPOT_FALLOFF", "SPOT_FULL",
+                   "EMITTER_BACK", "SPHERE_INSIDE", "END_PICKED", "END_OTHER", "END_SURFACE", "END_ESCAPED", "ENV_ADDED")
+    SURF_MATERIAL, SURF_REFLECT_CHANCE, SURF_MASKED_PROB, SURF_LIGHT, SURF_FIRST, SURF_VERTICES, SURF_NAN, SURF_EARLY_ESCAPE, SURF_LATE_ESCAPE, SURF_INSIDE_EPSILON, SURF_COUNTS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+    SURF_WORDS = SURF_COUNTS + len(SURF_EVENTS)
+
+    def surface(self, samples, setting=None):
+        """What the materials, the lights and the integrator did in li_replay, per record (n, 34): the first vertex's material type
+        + 1 (+ 16 under a mask; 0 where the camera ray escaped), the first transparent vertex's reflectChance, the first masked
+        vertex's maskedProb, the light picked at the first vertex + 1, the first vertex's events as a bit mask (bit i: SURF_EVENTS[i]),
+        the number of vertices, 1 for a NaN in li, the number of punched-through paths that escaped where the `firstBounce` rule adds the
+        environment and where it adds none, the number of light samples nearer than the fragment's epsilon (a negative shadow maxt), and per event the number of times any vertex noted it.  Returns (records, li)
+        with li what li_replay gives."""
+        s = setting or self.scene.desc.setting
+        samples = np.ascontiguousarray(samples, np.float32)
+        assert samples.shape[1] == self.dims(s), (samples.shape, self.dims(s))
+        out, li = np.zeros((samples.shape[0], self.SURF_WORDS), np.float32), np.zeros((samples.shape[0], 4), np.float32)
+        if lib().orc_surface(self.h, C.byref(s), _ptr(samples), samples.shape[0], _ptr(out), _ptr(li)) != 0:
+            raise RuntimeError("orc_surface failed")
         return out, li
 
     def splat(self, samples, li, film=None):
