@@ -354,7 +354,7 @@ void gbl_destroy(gbl_ctx* ctx) {
     for (void* p : ctx->allocations) (void)hipFree(p);
     for (gbl_buf* b : {&ctx->li, &ctx->prim_hits, &ctx->prim_items, &ctx->vol, &ctx->sss, &ctx->aov, &ctx->stream_scratch, &ctx->stream_xy, &ctx->wf_spill,
                        &ctx->dev_rgb1, &ctx->dev_rgb, &ctx->dev_logs, &ctx->dev_filter, &ctx->denoise, &ctx->temporal, &ctx->motion, &ctx->motion_deform, &ctx->vertex_words, &ctx->pose_words,
-                       &ctx->lbvh_scratch, &ctx->tree_stats, &ctx->inst_stage, &ctx->query_spill})
+                       &ctx->lbvh_scratch, &ctx->tree_stats, &ctx->inst_stage, &ctx->query_spill, &ctx->query_any})
         if (b->p) (void)hipFree(b->p);
     if (ctx->stream_seeds) (void)hipFree(ctx->stream_seeds);
     if (ctx->wf_ev_shade) (void)hipEventDestroy(ctx->wf_ev_shade);

@@ -21,6 +21,7 @@
 #include "kernels/refit_args.h"
 #include "kernels/vertices_args.h"
 #include "kernels/query_args.h"
+#include "kernels/query_filtered_args.h"
 #include "kernels/pyramid_args.h"
 #include "kernels/environment_args.h"
 #include "kernels/materials_args.h"
@@ -131,6 +132,7 @@ struct gbl_ctx {
     uint32_t* d_mesh_tri_offset = nullptr;   // gbl_mesh::tri_offset per mesh on the device, made at the first query: a hit's primitive number
     gbl_buf query_spill;                     // the query kernels' stack levels beyond LDS, one column per thread of the largest grid
     std::map<std::pair<const void*, size_t>, int> query_occupancy;   // resident workgroups per CU by (kernel, dynamic LDS bytes), asked once each
+    gbl_buf query_any;                       // a transmittance query of a scene without masks: the any-hit bytes it is rewritten from
     // what gbl_update_lights needs to pack the light tables again (api_lights.hip, scene_prep.h repack_lights)
     std::vector<gbl_light> h_lights;         // the description last set: gbl_create's at first (gbl_get_lights)
     std::vector<DevLight> h_dev_lights;      // the device's light records, light_cdf and light_pick_pdf as last queued ...
@@ -208,6 +210,7 @@ typedef void (*gbl_li_kernel)(DevScene, RenderArgs, float4*);
 typedef void (*gbl_aov_kernel)(DevScene, RenderArgs, AovArgs);
 typedef void (*gbl_motion_kernel)(DevScene, MotionArgs);
 typedef void (*gbl_query_kernel)(DevScene, QueryArgs);
+typedef void (*gbl_query_filtered_kernel)(DevScene, FilteredQueryArgs);
 
 // kernels_path.hip: the persistent megakernel and the AO kernel (kernels/render_kernels.h), native / replay samplers
 gbl_render_kernel gbl_kernel_path(bool replay, bool stats, bool ext, bool exact_ties = false);
@@ -272,6 +275,12 @@ void gbl_launch_temporal_accumulate_motion(bool spatial, const float4* cl, const
 // one-ray-per-lane measurement form (-DGBL_QUERY_PLAIN), which takes the whole stack in LDS and no hot prefix.
 gbl_query_kernel gbl_kernel_query(bool any, bool ext, bool ties, bool normal);
 bool gbl_query_plain(void);
+// kernels_query_filtered.hip: gbl_trace_rays_filtered's kernels (kernels/query_filtered.h), EXT builds all -- closest-hit (with or
+// without the normal), any-hit or transmittance, each with or without the tie rule (nullptr for the normal with anything but
+// closest-hit) -- and the two fills that answer a scene without masks
+gbl_query_filtered_kernel gbl_kernel_query_filtered(uint32_t kind, bool ties, bool normal);
+void gbl_launch_query_fill_miss(float4* hits, uint32_t n, hipStream_t stream);
+void gbl_launch_query_any_to_transmittance(const uint8_t* occluded, float4* out, uint32_t n, hipStream_t stream);
 // kernels_pyramid.hip: one level of an edited image's MIP pyramid from the level above it (kernels/pyramid.h)
 void gbl_launch_pyramid_level(const PyramidArgs& a, hipStream_t stream);
 // kernels_environment.hip: an image based light's distribution, power and the pick distribution from its image's pyramid

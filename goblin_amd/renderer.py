@@ -568,16 +568,23 @@ class HipPathTracer:
             at += h * w * c
         return record, levels
 
-    def _query_flags(self, kind, exact_ties, normals):
-        if kind not in ("closest", "any"):
-            raise ValueError("kind must be 'closest' or 'any', got %r" % (kind,))
-        if normals and kind == "any":
-            raise ValueError("normals need kind='closest': an any-hit query has no hit to shade")
-        return (_abi.GBL_QUERY_ANY if kind == "any" else _abi.GBL_QUERY_CLOSEST,
+    _QUERY_KINDS = {"closest": _abi.GBL_QUERY_CLOSEST, "any": _abi.GBL_QUERY_ANY, "transmittance": _abi.GBL_QUERY_TRANSMITTANCE}
+    _QUERY_FILTERS = {"none": _abi.GBL_QUERY_FILTER_NONE, "opaque": _abi.GBL_QUERY_FILTER_OPAQUE, "mask": _abi.GBL_QUERY_FILTER_MASK}
+
+    def _query_flags(self, kind, exact_ties, normals, filter="none"):
+        if kind not in self._QUERY_KINDS:
+            raise ValueError("kind must be 'closest', 'any' or 'transmittance', got %r" % (kind,))
+        if filter not in self._QUERY_FILTERS:
+            raise ValueError("filter must be 'none', 'opaque' or 'mask', got %r" % (filter,))
+        if normals and kind != "closest":
+            raise ValueError("normals need kind='closest': an any-hit or a transmittance query has no hit to shade")
+        if kind == "transmittance" and filter != "none":
+            raise ValueError("kind='transmittance' takes filter='none': it filters by itself")
+        return (self._QUERY_KINDS[kind],
                 (_abi.GBL_QUERY_EXACT_TIES if exact_ties else 0) | (_abi.GBL_QUERY_SHADING_NORMAL if normals else 0))
 
-    def trace(self, rays, kind="closest", exact_ties=False, normals=False, out=None, stream=None, _max_workgroups=None):
-        """Scene queries for a batch of rays (gbl_trace_rays) against the scene as edited so far.
+    def trace(self, rays, kind="closest", exact_ties=False, normals=False, out=None, stream=None, _max_workgroups=None, filter="none"):
+        """Scene queries for a batch of rays (gbl_trace_rays, gbl_trace_rays_filtered) against the scene as edited so far.
 
         ``rays``: a contiguous float32 (n, 8) tensor on the tracer's device -- columns origin, mint, direction, maxt, which is
         gbl_ray's layout -- read where it lies.  The direction need not be normalised; t is in its units.
@@ -585,15 +592,21 @@ class HipPathTracer:
         kind="closest": a dict of views over one (n, 8) float32 output tensor (``out``, or a new one; the dict's "records"):
         t (-1: miss), b1, b2, instance (int32, -1: miss), primitive (int32: the triangle's number within its mesh), normal
         ((n, 3): the world-space shading normal with ``normals``, zeros without).  kind="any": an (n,) uint8 tensor, 1 occluded.
+        ``filter``: "opaque" leaves out every instance whose material is a mask, as the integrator's shadow rays do; "mask"
+        keeps only those.  kind="transmittance": what the path tracer multiplies a light sample by along the segment -- a dict
+        over one (n, 4) float32 tensor ("records"): tr ((n, 3) view), crossed (int32: the mask surfaces multiplied in),
+        occluded (bool: an opaque surface blocks the segment; tr is then zero).
         ``exact_ties``: the reference's answer bit for bit.  Queued on ``stream`` (a torch stream; the current one by
-        default); does not synchronise."""
+        default); does not synchronise.  With the defaults of ``filter`` and a kind other than "transmittance" the call is
+        gbl_trace_rays."""
         torch = _torch()
-        k, flags = self._query_flags(kind, exact_ties, normals)
+        k, flags = self._query_flags(kind, exact_ties, normals, filter)
+        filtered = kind == "transmittance" or filter != "none"
         if rays.dtype != torch.float32 or rays.device != self.device or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
             raise ValueError("rays must be a contiguous float32 (n, 8) tensor on %s, got %s %s on %s%s" %
                              (self.device, rays.dtype, tuple(rays.shape), rays.device, "" if rays.is_contiguous() else ", not contiguous"))
         n = rays.shape[0]
-        want = (n,) if kind == "any" else (n, 8)
+        want = {"any": (n,), "closest": (n, 8), "transmittance": (n, 4)}[kind]
         dtype = torch.uint8 if kind == "any" else torch.float32
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         if out is None:
@@ -602,7 +615,13 @@ class HipPathTracer:
         elif out.dtype != dtype or out.device != self.device or tuple(out.shape) != want or not out.is_contiguous():
             raise ValueError("out must be a contiguous %s %s tensor on %s" % (dtype, want, self.device))
         if n > 0:
-            if _max_workgroups is None:
+            if filtered:
+                f = self._QUERY_FILTERS[filter]
+                if _max_workgroups is None:
+                    st = self.lib.gbl_trace_rays_filtered(self.handle, k, f, rays.data_ptr(), n, out.data_ptr(), flags, s.cuda_stream)
+                else:
+                    st = self.lib.gbl_selftest_query_filtered(self.handle, k, f, rays.data_ptr(), n, out.data_ptr(), flags, int(_max_workgroups))
+            elif _max_workgroups is None:
                 st = self.lib.gbl_trace_rays(self.handle, k, rays.data_ptr(), n, out.data_ptr(), flags, s.cuda_stream)
             else:
                 st = self.lib.gbl_selftest_query(self.handle, k, rays.data_ptr(), n, out.data_ptr(), flags, int(_max_workgroups))
@@ -611,6 +630,9 @@ class HipPathTracer:
         if kind == "any":
             return out
         ints = out.view(torch.int32)
+        if kind == "transmittance":
+            with torch.cuda.stream(s):   # (the two derived tensors are made behind the query, on its stream)
+                return {"records": out, "tr": out[:, 0:3], "crossed": ints[:, 3] & 0x7fffffff, "occluded": ints[:, 3] < 0}
         return {"records": out, "t": out[:, 0], "b1": out[:, 1], "b2": out[:, 2], "instance": ints[:, 3], "primitive": ints[:, 4],
                 "normal": out[:, 5:8]}
 

@@ -1085,8 +1085,8 @@ gbl_status gbl_selftest_environment(gbl_ctx* ctx, uint32_t light, float* dist_ou
  *    deepened the tree past that backing, its reallocation (a free and an allocation, which wait for the device).  The per-lane
  *    stacks beyond 16 levels live in that buffer of the context: queries of one context are queued on one stream at a time, like
  *    its renders.
- *  - Limit: queries are unfiltered.  The surface of a mask material counts as a surface (the reference's isOpaque filter, which
- *    its shadow rays use, is not offered); see DESIGN.md 9.
+ *  - Queries of this entry are unfiltered: the surface of a mask material counts as a surface.  The reference's isOpaque /
+ *    notOpaque filters and the transmittance its shadow rays take are gbl_trace_rays_filtered's, below.
  * Refusals, nothing launched: GBL_ERR_INVALID for a NULL ctx, a NULL pointer with n > 0, an unknown kind, unknown bits in flags,
  * GBL_QUERY_SHADING_NORMAL with GBL_QUERY_ANY, a pointer that is not device or managed memory of the context's device (a plain
  * host pointer is refused before anything reads it) or whose allocation ends before 32 n bytes (n bytes for the any-hit
@@ -1106,6 +1106,40 @@ gbl_status gbl_trace_rays(gbl_ctx* ctx, uint32_t kind, const gbl_ray* d_rays, ui
  * path a plain call only reaches at hundreds of thousands of rays. */
 gbl_status gbl_selftest_query(gbl_ctx* ctx, uint32_t kind, const gbl_ray* d_rays, uint64_t n, void* d_out, uint32_t flags,
                               uint32_t max_workgroups);
+
+/* Filtered scene queries: gbl_trace_rays under the reference's IntersectFilter, and the transmittance of a shadow segment as
+ * PathTracer::Li takes it -- what a caller's shadow rays need to agree with the integrator in a scene of cut-outs, tinted panes and
+ * decals.  Rays, records, flags, stream order, synchronisation points and refusals are gbl_trace_rays'; what is added:
+ *  - filter, for GBL_QUERY_CLOSEST and GBL_QUERY_ANY.  GBL_QUERY_FILTER_NONE is gbl_trace_rays itself: the same kernels, the same
+ *    bytes.  GBL_QUERY_FILTER_OPAQUE skips every instance whose material is a mask (or a subsurface material, which the
+ *    reference marks the same way) whole, as Model::intersect does under isOpaque; GBL_QUERY_FILTER_MASK skips every other
+ *    instance (notOpaque).  The answer is that of gbl_trace_rays on a scene with the skipped instances removed, `instance` still
+ *    numbering the whole scene's.  An instance is on one side by its material's TYPE: a mask whose alpha is 1 is still a mask.
+ *  - kind GBL_QUERY_TRANSMITTANCE (filter must be GBL_QUERY_FILTER_NONE, GBL_QUERY_SHADING_NORMAL is refused) writes n
+ *    gbl_ray_transmittance records.  If an opaque surface lies within [mint, maxt] -- Scene::occluded(ray, isOpaque) -- tr is
+ *    {0, 0, 0} and crossed is 0x80000000.  Otherwise tr is PathTracer::evalAttenuation's product over the mask surfaces of the
+ *    segment, front to back: (1 - alpha) * transparent_color per surface, alpha and colour looked up at the hit as a render does,
+ *    mint moved to t + epsilon behind each; the walk ends at Black (a mask that wraps a subsurface material answers Black) or
+ *    after 1024 surfaces; crossed counts the factors multiplied in.  An invalid ray answers {1, 1, 1}, 0.
+ *    GBL_QUERY_EXACT_TIES governs the occlusion query; the walk's own closest-hit queries follow the reference's tie rule always,
+ *    as a render's do, so a pending tie order is made (one synchronisation) by every transmittance query.
+ *  - A scene without a mask material launches no filtered traversal: OPAQUE is NONE, MASK misses everywhere, TRANSMITTANCE is the
+ *    any-hit answer rewritten as {1, 1, 1}, 0 or {0, 0, 0}, 0x80000000 (through n bytes of the context's own, grown on demand).
+ *  - Limit: where two instances on the same side of the filter are met at exactly the same t, which one is reported is the
+ *    traversal order's choice, as in gbl_trace_rays; DESIGN.md 4.11.
+ * Further refusals, nothing launched: GBL_ERR_INVALID for an unknown filter, for GBL_QUERY_TRANSMITTANCE with a filter other than
+ * GBL_QUERY_FILTER_NONE or with GBL_QUERY_SHADING_NORMAL, and for a transmittance output whose allocation ends before 16 n bytes. */
+#define GBL_QUERY_FILTER_NONE   0u
+#define GBL_QUERY_FILTER_OPAQUE 1u   /* instances whose material is a mask are skipped whole: Model::intersect under isOpaque */
+#define GBL_QUERY_FILTER_MASK   2u   /* only those instances: notOpaque */
+#define GBL_QUERY_TRANSMITTANCE 2u   /* kind, accepted by gbl_trace_rays_filtered only */
+typedef struct gbl_ray_transmittance { float tr[3]; uint32_t crossed; } gbl_ray_transmittance;  /* 16 B */
+gbl_status gbl_trace_rays_filtered(gbl_ctx* ctx, uint32_t kind, uint32_t filter, const gbl_ray* d_rays, uint64_t n,
+                                   void* d_out /* CLOSEST: n gbl_ray_hit; ANY: n bytes; TRANSMITTANCE: n gbl_ray_transmittance */,
+                                   uint32_t flags, void* stream);
+/* Self-test hook: gbl_trace_rays_filtered as gbl_selftest_query is gbl_trace_rays. */
+gbl_status gbl_selftest_query_filtered(gbl_ctx* ctx, uint32_t kind, uint32_t filter, const gbl_ray* d_rays, uint64_t n, void* d_out,
+                                       uint32_t flags, uint32_t max_workgroups);
 
 /* Self-test hook: the device's sinf / cosf (glibc's algorithm restated, kernels/refmath.h) on n device floats. */
 gbl_status gbl_selftest_sincos(gbl_ctx* ctx, const float* in, float* sin_out, float* cos_out, uint64_t n);
