@@ -208,6 +208,15 @@ class gbl_ray_transmittance(C.Structure):
     _fields_ = [("tr", C.c_float * 3), ("crossed", C.c_uint32)]
 
 
+GBL_RADIANCE_EXACT_TIES, GBL_RADIANCE_RUSSIAN_ROULETTE = 1, 2   # gbl_radiance_params.flags
+
+
+class gbl_radiance_params(C.Structure):
+    _fields_ = [("max_ray_depth", C.c_int32), ("samples_per_group", C.c_uint32), ("first_group", C.c_uint32), ("flags", C.c_uint32),
+                ("seed", C.c_uint64), ("d_records", C.c_void_p), ("record_stride", C.c_uint32), ("reserved", C.c_uint32),
+                ("stream", C.c_void_p)]
+
+
 class gbl_info(C.Structure):
     _fields_ = [("xres", C.c_int32), ("yres", C.c_int32), ("window", C.c_int32 * 4), ("blas_nodes", C.c_uint64),
                 ("tlas_nodes", C.c_uint64), ("triangles", C.c_uint64), ("instances", C.c_uint64),
@@ -222,7 +231,7 @@ HOST_SYMBOLS = ["gbl_host_load_file", "gbl_host_load_string", "gbl_host_desc", "
                 "gbl_host_read_image", "gbl_host_free_image"]
 GBL_CREATE_DEVICE_BVH = 1
 GBL_INSTANCES_DEVICE_TLAS = 1
-HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_rebuild_mesh", "gbl_mesh_tree_stats", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_update_instances_device", "gbl_get_instances_device", "gbl_selftest_instances", "gbl_update_lights", "gbl_get_lights", "gbl_selftest_lights", "gbl_update_materials", "gbl_get_materials", "gbl_update_textures", "gbl_get_textures", "gbl_update_materials_device", "gbl_update_textures_device", "gbl_selftest_materials", "gbl_update_image_device", "gbl_update_environment_device", "gbl_update_environment", "gbl_selftest_environment", "gbl_update_image", "gbl_get_image", "gbl_trace_rays", "gbl_selftest_query", "gbl_trace_rays_filtered", "gbl_selftest_query_filtered", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
+HIP_SYMBOLS = ["gbl_create", "gbl_create_ex", "gbl_update_instances", "gbl_update_camera", "gbl_get_camera", "gbl_film_accumulate", "gbl_get_instances", "gbl_update_vertices", "gbl_get_vertices", "gbl_update_vertices_device", "gbl_get_vertices_device", "gbl_order_pending", "gbl_rebuild_mesh", "gbl_mesh_tree_stats", "gbl_render_motion_deform_device", "gbl_selftest_geometry", "gbl_update_instances_device", "gbl_get_instances_device", "gbl_selftest_instances", "gbl_update_lights", "gbl_get_lights", "gbl_selftest_lights", "gbl_update_materials", "gbl_get_materials", "gbl_update_textures", "gbl_get_textures", "gbl_update_materials_device", "gbl_update_textures_device", "gbl_selftest_materials", "gbl_update_image_device", "gbl_update_environment_device", "gbl_update_environment", "gbl_selftest_environment", "gbl_update_image", "gbl_get_image", "gbl_trace_rays", "gbl_selftest_query", "gbl_trace_rays_filtered", "gbl_selftest_query_filtered", "gbl_radiance_rays", "gbl_selftest_radiance", "gbl_render_motion", "gbl_render_motion_deform", "gbl_film_accumulate_motion", "gbl_render", "gbl_film_allreduce", "gbl_film_resolve", "gbl_film_develop", "gbl_render_aov",
                "gbl_aov_resolve_depth", "gbl_film_variance", "gbl_film_denoise", "gbl_get_info", "gbl_destroy",
                "gbl_last_error", "gbl_abi_version", "gbl_get_timings", "gbl_selftest_sincos", "gbl_selftest_trace", "gbl_selftest_arith", "gbl_selftest_libm", "gbl_selftest_valu_issue"]
 
@@ -352,6 +361,8 @@ def hip_lib():
         lib.gbl_selftest_query.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.gbl_trace_rays_filtered.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.gbl_selftest_query_filtered.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.gbl_radiance_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gbl_radiance_params), C.c_void_p]
+        lib.gbl_selftest_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(gbl_radiance_params), C.c_void_p, C.c_uint32]
         lib.gbl_update_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
         lib.gbl_get_camera.argtypes = [C.c_void_p, C.POINTER(gbl_camera)]
         lib.gbl_get_info.argtypes = [C.c_void_p, C.POINTER(gbl_info)]

@@ -20,7 +20,7 @@ HOST_DEPS = HOST_SOURCES + [os.path.join(CSRC, "host", "json_lite.h"), os.path.j
 # what changed -- hipcc's depfiles decide).
 HIP_SOURCES = [os.path.join(CSRC, f) for f in
                ("api_context.hip", "api_render.hip", "api_aov.hip", "api_film.hip", "kernels_path.hip", "kernels_quad.hip", "kernels_stream.hip", "kernels_wavefront.hip",
-                "kernels_whitted.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_temporal.hip", "kernels_motion.hip", "api_motion.hip", "api_geometry.hip", "kernels_refit.hip", "kernels_vertices.hip", "api_instances.hip", "kernels_instances.hip", "api_lights.hip", "api_query.hip", "kernels_query.hip", "kernels_query_filtered.hip", "api_images.hip", "kernels_pyramid.hip", "api_environment.hip", "kernels_environment.hip", "api_materials.hip", "kernels_materials.hip", "scene_refit.cpp", "motion_stage.cpp",
+                "kernels_whitted.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_temporal.hip", "kernels_motion.hip", "api_motion.hip", "api_geometry.hip", "kernels_refit.hip", "kernels_vertices.hip", "api_instances.hip", "kernels_instances.hip", "api_lights.hip", "api_query.hip", "kernels_query.hip", "kernels_query_filtered.hip", "api_radiance.hip", "kernels_radiance.hip", "api_images.hip", "kernels_pyramid.hip", "api_environment.hip", "kernels_environment.hip", "api_materials.hip", "kernels_materials.hip", "scene_refit.cpp", "motion_stage.cpp",
                 "scene_prep.cpp")]
 OBJ = os.path.join(LIB, "obj")
 
@@ -34,7 +34,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # only IEEE mul / add and the explicit __builtin_fmaf get paired.
 _NO_SLP = ["-fno-slp-vectorize"]
 UNIT_FLAGS = {"kernels_quad": _NO_SLP, "kernels_path": _NO_SLP, "kernels_wavefront": _NO_SLP, "kernels_stream": _NO_SLP,
-              "kernels_whitted": _NO_SLP, "kernels_aux": _NO_SLP, "kernels_aov": _NO_SLP, "kernels_motion": _NO_SLP, "kernels_query": _NO_SLP, "kernels_query_filtered": _NO_SLP, "kernels_pyramid": _NO_SLP,
+              "kernels_whitted": _NO_SLP, "kernels_aux": _NO_SLP, "kernels_aov": _NO_SLP, "kernels_motion": _NO_SLP, "kernels_query": _NO_SLP, "kernels_query_filtered": _NO_SLP, "kernels_radiance": _NO_SLP, "kernels_pyramid": _NO_SLP,
               "kernels_environment": _NO_SLP, "kernels_materials": _NO_SLP}
 
 

@@ -199,7 +199,7 @@ void set_scene_header(DevScene& sc, const PackedScene& packed) {
 // The host copies the edit entry points work from, grouped as gbl_ctx declares them (gbl_internal.h)
 void keep_for_edits(gbl_ctx* ctx, const gbl_scene_desc* desc, const PackedScene& packed) {
     // camera and film: gbl_update_camera, gbl_film_accumulate
-    ctx->h_camera = desc->camera, ctx->h_film = desc->film;
+    ctx->h_camera = desc->camera, ctx->h_film = desc->film, ctx->h_setting = desc->setting;
     ctx->scene_extended = packed.scene_extended;
     // instances and TLAS: gbl_update_instances and every edit that ends in its tail (api_instances.hip)
     ctx->h_instances.assign(desc->instances, desc->instances + desc->num_instances);

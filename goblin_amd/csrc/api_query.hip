@@ -37,7 +37,10 @@ gbl_status ensure_query_spill(gbl_ctx* ctx) {
     return grow(ctx, ctx->query_spill, static_cast<uint64_t>(deep) * level_bytes, "query stack backing");
 }
 
-// A call's buffers, as both entry points refuse them (n > 0): null pointers, 2^32 rays or more, memory that is not the device's or
+}   // namespace
+
+// (gbl_host.h: gbl_radiance_rays checks its buffers and lays its launch out the same way)
+// A call's buffers, as the entry points refuse them (n > 0): null pointers, 2^32 rays or more, memory that is not the device's or
 // ends early, an output that overlaps the rays.  Sets the device.
 gbl_status check_query_buffers(gbl_ctx* ctx, const std::string& who, const gbl_ray* d_rays, uint64_t n, void* d_out, uint64_t out_stride) {
     if (!d_rays || !d_out) return fail(ctx, GBL_ERR_INVALID, who + ": null pointer with n > 0");
@@ -80,6 +83,8 @@ gbl_status persistent_layout(gbl_ctx* ctx, const void* kernel, uint64_t n, uint3
     *lds_out = lds;
     return GBL_OK;
 }
+
+namespace {
 
 // gbl_trace_rays behind its refusals: n > 0 rays through the unfiltered kernels
 gbl_status launch_unfiltered(gbl_ctx* ctx, const std::string& who, bool any, bool ties, bool normal, const gbl_ray* d_rays, uint64_t n, void* d_out,

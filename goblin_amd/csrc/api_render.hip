@@ -327,7 +327,9 @@ std::vector<uint32_t> glibc_rand_sequence(size_t n) {
     return out;
 }
 
-// The sample quota of a camera sample: record dimensions and pattern offsets of the integrator (RenderArgs)
+}   // namespace
+
+// The sample quota of a camera sample: record dimensions and pattern offsets of the integrator (RenderArgs; gbl_host.h)
 void sample_layout(const DevScene& sc, const gbl_render_params* p, RenderArgs& ra) {
     ra.integrator = static_cast<int32_t>(p->integrator);
     ra.spp = round_to_square(p->sample_per_pixel, &ra.root);
@@ -362,7 +364,7 @@ void sample_layout(const DevScene& sc, const gbl_render_params* p, RenderArgs& r
     }
 }
 
-}   // namespace
+uint32_t native_seed_key(uint64_t seed) { return host_mix(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)); }
 
 // ---------------------------------------------------------------------------
 // What gbl_render shares with gbl_render_aov (gbl_host.h)
@@ -408,7 +410,7 @@ gbl_status plan_samples(gbl_ctx* ctx, const gbl_render_params* p, bool check_sch
     if (ra.shard_index < 0 || ra.shard_index >= ra.shard_count) return fail(ctx, GBL_ERR_INVALID, "tile_shard_index out of range");
     pl->total_tiles = ra.tiles_x * ra.tiles_y;
     ra.local_tiles = pl->total_tiles > ra.shard_index ? (pl->total_tiles - ra.shard_index + ra.shard_count - 1) / ra.shard_count : 0;
-    ra.seed_key = host_mix(static_cast<uint32_t>(p->seed), static_cast<uint32_t>(p->seed >> 32));
+    ra.seed_key = native_seed_key(p->seed);
     ra.replay = p->replay_samples;
     ra.work_counter = ctx->work_counter;
     ra.stats = ctx->stats;

@@ -1,5 +1,5 @@
 // Internal to libgoblin_hip.so, host side only: what the units behind the C ABI (api_context.hip, api_render.hip, api_aov.hip,
-// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip, api_images.hip, api_environment.hip, api_materials.hip) share.  No kernel header is needed to read it.
+// api_film.hip, api_motion.hip, api_geometry.hip, api_instances.hip, api_lights.hip, api_query.hip, api_radiance.hip, api_images.hip, api_environment.hip, api_materials.hip) share.  No kernel header is needed to read it.
 #pragma once
 #include <chrono>
 #include <cstdlib>
@@ -115,6 +115,19 @@ struct SamplePlan {
 // the sample counts and the window; gbl_render_aov ignores that field.  A shard that owns no tile leaves with
 // ra.local_tiles == 0.  Nothing is launched or allocated.  (api_render.hip)
 gbl_status plan_samples(gbl_ctx* ctx, const gbl_render_params* p, bool check_schedule, SamplePlan* pl);
+
+// The sample quota of a camera sample of `p`'s integrator: ra.spp / root, max_depth, the replay record's dims and off2_base and the
+// BSSRDF block's offsets.  RenderArgs::seed_key of a caller's seed.  gbl_radiance_rays takes both as gbl_render does.  (api_render.hip)
+void sample_layout(const DevScene& sc, const gbl_render_params* p, RenderArgs& ra);
+uint32_t native_seed_key(uint64_t seed);
+
+// The buffers of a query call with n > 0 rays: null pointers, 2^32 rays or more, memory that is not the device's or ends early, an
+// output of n records of out_stride bytes that overlaps the rays.  Sets the device.  (api_query.hip)
+gbl_status check_query_buffers(gbl_ctx* ctx, const std::string& who, const gbl_ray* d_rays, uint64_t n, void* d_out, uint64_t out_stride);
+// A persistent ray kernel's launch: the stack backing and the LDS layout (stacks' first levels, then the top of the tree) into
+// qa's stack_spill / hot_word / hot_count, the resident workgroups from the context's occupancy cache into *wgs, the LDS bytes into
+// *lds.  max_workgroups: 0 for the grid the device holds.  (api_query.hip)
+gbl_status persistent_layout(gbl_ctx* ctx, const void* kernel, uint64_t n, uint32_t max_workgroups, QueryArgs& qa, size_t* lds_out, uint64_t* wgs_out);
 
 // The register-accumulating splat (kernels/wavefront.h wf_splat) of per-sample values into ra.film: samples pass_k0 ..
 // pass_k0 + pass_spp of every pixel of the shard's tiles, `li` holding pass_spp values per pixel of the window.  (api_render.hip)

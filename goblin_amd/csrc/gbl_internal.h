@@ -22,6 +22,7 @@
 #include "kernels/vertices_args.h"
 #include "kernels/query_args.h"
 #include "kernels/query_filtered_args.h"
+#include "kernels/radiance_args.h"
 #include "kernels/pyramid_args.h"
 #include "kernels/environment_args.h"
 #include "kernels/materials_args.h"
@@ -80,6 +81,7 @@ struct gbl_ctx {
     // what gbl_update_camera and gbl_film_accumulate need to pack a camera (scene_prep.h pack_camera)
     gbl_camera h_camera;      // the description last set: gbl_create's at first (gbl_get_camera)
     gbl_film h_film;
+    gbl_render_setting h_setting;   // gbl_create's render_setting block: its bssrdf_sample_num sizes a replay record (gbl_radiance_rays)
     int32_t scene_extended = 0;   // DevScene::extended without the camera's part
     // what gbl_update_instances needs to rebuild the TLAS
     std::vector<gbl_instance> h_instances;
@@ -211,6 +213,7 @@ typedef void (*gbl_aov_kernel)(DevScene, RenderArgs, AovArgs);
 typedef void (*gbl_motion_kernel)(DevScene, MotionArgs);
 typedef void (*gbl_query_kernel)(DevScene, QueryArgs);
 typedef void (*gbl_query_filtered_kernel)(DevScene, FilteredQueryArgs);
+typedef void (*gbl_radiance_kernel)(DevScene, RadianceArgs);
 
 // kernels_path.hip: the persistent megakernel and the AO kernel (kernels/render_kernels.h), native / replay samplers
 gbl_render_kernel gbl_kernel_path(bool replay, bool stats, bool ext, bool exact_ties = false);
@@ -281,6 +284,9 @@ bool gbl_query_plain(void);
 gbl_query_filtered_kernel gbl_kernel_query_filtered(uint32_t kind, bool ties, bool normal);
 void gbl_launch_query_fill_miss(float4* hits, uint32_t n, hipStream_t stream);
 void gbl_launch_query_any_to_transmittance(const uint8_t* occluded, float4* out, uint32_t n, hipStream_t stream);
+// kernels_radiance.hip: gbl_radiance_rays' kernels (kernels/radiance.h) -- native or replay draws, lean or EXT; exact_ties picks the
+// lean native build with the tie rule (the replay and EXT builds follow it always)
+gbl_radiance_kernel gbl_kernel_radiance(bool replay, bool ext, bool exact_ties);
 // kernels_pyramid.hip: one level of an edited image's MIP pyramid from the level above it (kernels/pyramid.h)
 void gbl_launch_pyramid_level(const PyramidArgs& a, hipStream_t stream);
 // kernels_environment.hip: an image based light's distribution, power and the pick distribution from its image's pyramid

@@ -636,6 +636,51 @@ class HipPathTracer:
         return {"records": out, "t": out[:, 0], "b1": out[:, 1], "b2": out[:, 2], "instance": ints[:, 3], "primitive": ints[:, 4],
                 "normal": out[:, 5:8]}
 
+    def radiance(self, rays, depth=None, seed=0, samples_per_group=1, first_group=0, records=None, exact_ties=False, rr=False,
+                 out=None, stream=None, _max_workgroups=None):
+        """Path-traced radiance along a batch of rays (gbl_radiance_rays) against the scene as edited so far: PathTracer::Li.
+
+        ``rays``: as ``trace`` takes them, a contiguous float32 (n, 8) tensor on the tracer's device, but the direction MUST be a
+        unit vector.  Returns an (n, 4) float32 tensor (``out``, or a new one): {r, g, b, 1} per ray, {0, 0, 0, 0} for an invalid
+        ray; a NaN component is stored as it is.  ``depth``: the path tracer's max_ray_depth (None: the scene's; 1 = emission and
+        environment only).
+        Native draws: ray i is sample i % samples_per_group of group first_group + i // samples_per_group -- a group is to this
+        call what a pixel is to ``render``, its samples stratified against each other (a probe is a group of directions, a
+        lightmap texel a group of positions); ``seed``, ``rr`` and ``exact_ties`` are ``render``'s.  ``records``: a contiguous
+        float32 (n, dims) tensor on the device of replay records in ``render``'s layout at this depth instead (their first
+        four floats are not read).  Queued on ``stream`` (a torch stream; the current one by default); does not synchronise.
+        The mean of a group: ``out.view(-1, samples_per_group, 4).mean(1)``."""
+        torch = _torch()
+        if rays.dtype != torch.float32 or rays.device != self.device or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous float32 (n, 8) tensor on %s, got %s %s on %s%s" %
+                             (self.device, rays.dtype, tuple(rays.shape), rays.device, "" if rays.is_contiguous() else ", not contiguous"))
+        n = rays.shape[0]
+        p = _abi.gbl_radiance_params()
+        p.max_ray_depth = self.scene.desc.setting.max_ray_depth if depth is None else int(depth)
+        p.samples_per_group = int(samples_per_group)
+        p.first_group = int(first_group)
+        p.flags = (_abi.GBL_RADIANCE_EXACT_TIES if exact_ties else 0) | (_abi.GBL_RADIANCE_RUSSIAN_ROULETTE if rr else 0)
+        p.seed = int(seed)
+        if records is not None:
+            if records.dtype != torch.float32 or records.device != self.device or records.dim() != 2 or records.shape[0] != n or not records.is_contiguous():
+                raise ValueError("records must be a contiguous float32 (%d, dims) tensor on %s" % (n, self.device))
+            p.d_records = records.data_ptr()
+            p.record_stride = records.shape[1]
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        p.stream = s.cuda_stream
+        if out is None:
+            with torch.cuda.stream(s):   # (the caching allocator ties the block to the stream that uses it)
+                out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or tuple(out.shape) != (n, 4) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 (%d, 4) tensor on %s" % (n, self.device))
+        if _max_workgroups is None:
+            st = self.lib.gbl_radiance_rays(self.handle, rays.data_ptr(), n, C.byref(p), out.data_ptr())
+        else:
+            st = self.lib.gbl_selftest_radiance(self.handle, rays.data_ptr(), n, C.byref(p), out.data_ptr(), int(_max_workgroups))
+        if st != _abi.GBL_OK:
+            raise _abi.GoblinError(st, self.lib.gbl_last_error(self.handle).decode())
+        return out
+
     def __del__(self):
         h, self.handle = getattr(self, "handle", None), None
         if h:

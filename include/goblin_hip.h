@@ -1141,6 +1141,60 @@ gbl_status gbl_trace_rays_filtered(gbl_ctx* ctx, uint32_t kind, uint32_t filter,
 gbl_status gbl_selftest_query_filtered(gbl_ctx* ctx, uint32_t kind, uint32_t filter, const gbl_ray* d_rays, uint64_t n, void* d_out,
                                        uint32_t flags, uint32_t max_workgroups);
 
+/* Path-traced radiance along caller rays: PathTracer::Li (GoblinPathtracer.cpp:50-179) for n rays in device memory, against the
+ * scene as every edit so far left it -- what a probe, a lightmap texel, a rasteriser's reflection pass or a second view asks, without
+ * re-aiming the scene's one camera and reading a film back.
+ *  - Ray i is the ray Li receives: its first query is Scene::intersect over [mint, maxt] (maxt = +inf is the usual value), and a
+ *    first query that ends without a surface adds the environment as :61-65 does.  d must be a unit vector (every BSDF reads
+ *    wo = -d).  No vertex has ray differentials: the ray is a RayDifferential without auxiliary rays (GoblinRay.h:48-51), which
+ *    is what every continuation ray of the reference is, so trilinear and EWA lookups at vertex 0 see a zero footprint.  If the rays
+ *    are a frame's own camera rays, the answers are that frame's per-sample Li (gbl_render's li_out) bit for bit, but for those
+ *    lookups.
+ *  - d_out[i] = {Li.r, Li.g, Li.b, 1}.  A NaN component is stored as it is: the caller drops it, as ImageTile::addSample does.  An
+ *    invalid ray -- gbl_trace_rays' rule, or |d.d - 1| > 1e-4 -- answers {0, 0, 0, 0} and fetches no node.  A scene without lights
+ *    answers {0, 0, 0, 1} for every valid ray (:53-56).
+ *  - max_ray_depth is PathTracer's: the loop runs max_ray_depth - 1 times; 1 = emission / environment only.
+ *  - Native draws (d_records == NULL): ray i is sample k = i % S of group g = first_group + i / S, S = samples_per_group, and
+ *    draws what camera sample k of a pixel whose index in the full sample window is g draws under gbl_render_params.seed == seed
+ *    at S samples per pixel: vertex b takes the 1D patterns 3 b, 3 b + 1, 3 b + 2 and the 2D patterns 0x10000 + 2 b and + 1.  So a
+ *    group is to this call what a pixel is to gbl_render -- its S samples are stratified against each other -- and a batch split
+ *    over calls with matching first_group draws what one call would.  GBL_RADIANCE_RUSSIAN_ROULETTE and GBL_RADIANCE_EXACT_TIES
+ *    are gbl_render_params' russian_roulette and exact_ties.
+ *  - Replay draws (d_records != NULL): record i is ray i's, in gbl_render's replay layout for the path tracer at this max_ray_depth
+ *    in this scene (gbl_host_sample_dimension_scene floats; record_stride must equal that).  Its first four floats (image position,
+ *    lens) are not read.  first_group, seed and samples_per_group are then ignored, except that n % S == 0 still holds.
+ *  - Which builds read the tie order (gbl_update_vertices_device): every one but the lean native build without
+ *    GBL_RADIANCE_EXACT_TIES, which leaves a deferred order pending.
+ *  - Asynchronous on params->stream; no host synchronisation but gbl_trace_rays' (a pending tie order, the stack backing).  The
+ *    per-lane stacks beyond 16 levels live in the query kernels' buffer of the context, so no tree is too deep for the call, and
+ *    radiance calls and queries of one context are queued on one stream at a time.
+ * Refusals, nothing launched: GBL_ERR_INVALID for a NULL ctx or params, reserved != 0, unknown bits in flags, max_ray_depth
+ * outside [1, 16384] (above it the 1D pattern numbers reach the 2D patterns' base), samples_per_group not a perfect square in [1, 2^31),
+ * n % samples_per_group != 0, first_group + n / samples_per_group past 2^32, GBL_RADIANCE_RUSSIAN_ROULETTE with records, a wrong
+ * record_stride, and gbl_trace_rays' buffer refusals (the records included; d_out holds 16 n bytes); GBL_ERR_UNSUPPORTED for
+ * n >= 2^32 and for a scene with a participating medium or a subsurface material: the medium and Lsubsurface are computed per
+ * camera sample by kernels of their own, and radiance through fog without the fog would be silently wrong.  n == 0 is GBL_OK and
+ * does nothing.  Not offered: the Whitted and AO integrators, a per-ray depth or seed, the mean of a group's samples. */
+#define GBL_RADIANCE_EXACT_TIES       1u   /* lean scenes: the reference's tie rule, as gbl_render_params.exact_ties */
+#define GBL_RADIANCE_RUSSIAN_ROULETTE 2u   /* the build-side extension of gbl_render_params.russian_roulette; native draws only */
+typedef struct gbl_radiance_params {
+    int32_t  max_ray_depth;       /* PathTracer's: the loop runs max_ray_depth - 1 times; 1 = emission / environment only */
+    uint32_t samples_per_group;   /* S, a perfect square >= 1 */
+    uint32_t first_group;         /* the group number of ray 0 (a batch split over calls draws what one call would) */
+    uint32_t flags;
+    uint64_t seed;                /* native draws */
+    const float* d_records;       /* device, or NULL = native draws */
+    uint32_t record_stride;       /* floats per record when d_records != NULL */
+    uint32_t reserved;            /* 0 */
+    void* stream;                 /* hipStream_t, NULL = default */
+} gbl_radiance_params;
+gbl_status gbl_radiance_rays(gbl_ctx* ctx, const gbl_ray* d_rays, uint64_t n, const gbl_radiance_params* params,
+                             float* d_out /* device, n float4 */);
+/* Self-test hook: gbl_radiance_rays with its persistent grid capped at max_workgroups (0: no cap) and a device synchronise at the
+ * end, as gbl_selftest_query is gbl_trace_rays. */
+gbl_status gbl_selftest_radiance(gbl_ctx* ctx, const gbl_ray* d_rays, uint64_t n, const gbl_radiance_params* params, float* d_out,
+                                 uint32_t max_workgroups);
+
 /* Self-test hook: the device's sinf / cosf (glibc's algorithm restated, kernels/refmath.h) on n device floats. */
 gbl_status gbl_selftest_sincos(gbl_ctx* ctx, const float* in, float* sin_out, float* cos_out, uint64_t n);
 /* Self-test hook: out[i] = fn(a[i] [, b[i]]) on n device floats, fn one of the libm functions the reference's sampling code
